@@ -6,13 +6,20 @@ Ellis wormhole (rho = 1), 1920x1080, cap 4096 Euler steps, default camera (l = 5
 focal 15, diagonal 43), escape radius 100, delta 0.05, two procedural 8192x4096 RGBA8 skies
 resident in HBM.  The frame stays in HBM (no D2H inside the timed region).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Started WITHOUT a launcher (no WORLD_SIZE in the environment) and with --gpus N > 1 it launches itself under
-`python -m torch.distributed.run --nproc-per-node N` (one rank per GPU, rendezvous on 127.0.0.1).  It refuses to
-run when the node has fewer than N GPUs or when the rank count it ends up with is not --gpus: a run never
-reports fewer GPUs than it was asked for.
+Started WITHOUT a launcher (no WORLD_SIZE in the environment) and with --gpus N > 1 it starts
+`python -m torch.distributed.run --nproc-per-node N` on itself as a child process (one rank per GPU, rendezvous on
+127.0.0.1) and exits with the child's status.  It refuses to run when the node has fewer than N GPUs or when the rank
+count it ends up with is not --gpus: a run never reports fewer GPUs than it was asked for.
+
+A plain run does only what the headline figure needs: set-up, the warm-up, the K timed steps, the outputs of the last
+step (--dump-outputs DIR: DIR/frame.npy, the frame as float32 H x W x 3, and DIR/stats.npy, the step's counters as
+float64), and the line.  Its `roofline` is computed from the timed region's own HIP events and the committed PMC
+profile (profiles/traffic.json), null where that profile has no entry.  Every secondary figure -- the frame downloaded
+to host memory, multi-frame launches, the sustained run, the live PMC passes, `value_efficient`, `cpu_baseline`,
+`value_single_image_rows`, `video_e2e` -- is measured only with --full, whose --no-* options switch them off one by one.
 
 With N > 1 every rank renders its own K frames (video frames are independent: weak scaling, no
 data-path collective); the only communication on the data path is the RCCL broadcast of the two sky
@@ -21,10 +28,10 @@ on a communicator from curvis_ctx_rccl_comm_init; the ncclUniqueId travels over 
 The control plane (barriers, the max-over-ranks reduction, the per-rank table) is a gloo process group
 on the launcher's store: it comes up wherever torchrun does, and it is what the ranks use to AGREE on a
 fall-back (torch's nccl broadcast, then host-staged gloo) should RCCL fail on any of them -- the line
-then says so in `collective.via` / `collective.fallback_from`.  Rank 0 prints ONE JSON line; for N > 1
+then says so in `collective.via` / `collective.fallback_from`.  Rank 0 prints ONE JSON line; with --full, for N > 1
 it also carries `cpu_baseline`, `value_single_image_rows` (ONE configs[1] image split by rows over the
 N GPUs) and `video_e2e` (`curvis video --mode brute --devices N` on a 16N-frame rendition of configs[3]).
-At N = 1 the line also carries `value_efficient`: the reference's DEFAULT renderer (render_image_efficient, what its CLI
+With --full at N = 1 the line also carries `value_efficient`: the reference's DEFAULT renderer (render_image_efficient, what its CLI
 runs) at configs[3]'s poses -- frames/s with kernels only (one context, GPU-idle share from its HIP events) and end to end
 through `curvis video --mode efficient` on the reference's own path_orbit.csv; outside the contract's timed region.
 """
@@ -55,6 +62,12 @@ def parse():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--max-iter", type=int, default=4096)
     ap.add_argument("--metric", default="ellis", choices=["ellis", "interstellar"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary figure (download, multi-frame, sustained, live PMC passes, value_efficient, "
+                         "cpu_baseline; N > 1: rows split, video_e2e); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed: DIR/frame.npy (the frame, float32 "
+                         "H x W x 3) and DIR/stats.npy (rays, steps, escaped +l, escaped -l, neither, out-of-range texels; float64)")
     ap.add_argument("--sky", type=int, default=8192, help="sky width (height = width/2)")
     ap.add_argument("--variant", type=int, default=-1,
                     help="-1 library default (static kernel; relay kernel for big single frames), 1 static, 2 relay, 0 persistent lane-refill")
@@ -66,26 +79,27 @@ def parse():
                     help="copy every frame to host memory inside the timed region (PCIe-inclusive rate, "
                          "reported in DESIGN.md; never the headline value)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="report roofline.traffic as null when profiles/traffic.json has no entry for this workload "
-                         "(default: such a run fails, so a missing PMC profile cannot go unnoticed)")
+                    help="--full: report roofline.traffic as null when neither profiles/traffic.json nor the live PMC passes "
+                         "give a figure for this workload (default: such a run fails, so a missing PMC profile cannot go "
+                         "unnoticed; a plain run reports null)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not re-run this workload under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` after the "
+                    help="--full: do not re-run this workload under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` after the "
                          "timed region (two short child runs, N = 1 only); roofline.traffic then comes from the "
-                         "committed profile alone")
+                         "committed profile alone, as in a plain run")
     ap.add_argument("--multi-frame", type=int, default=6,
-                    help="frames per launch of the secondary multi-frame measurement (value_multi_frame); 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: frames per launch of the secondary multi-frame measurement (value_multi_frame); 0 = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--no-video-e2e", action="store_true",
-                    help="N > 1: skip the `curvis video --mode brute --devices N` end-to-end figure (video_e2e)")
+                    help="--full, N > 1: skip the `curvis video --mode brute --devices N` end-to-end figure (video_e2e)")
     ap.add_argument("--video-e2e-frames-per-gpu", type=int, default=16)
     ap.add_argument("--no-rows-split", action="store_true",
-                    help="N > 1: skip value_single_image_rows (one image split by rows over the ranks)")
+                    help="--full, N > 1: skip value_single_image_rows (one image split by rows over the ranks)")
     ap.add_argument("--sustained-seconds", type=float, default=10.0,
-                    help="length of the secondary back-to-back measurement behind `value_sustained` (clock and power "
+                    help="--full: length of the secondary back-to-back measurement behind `value_sustained` (clock and power "
                          "sampled during it); 0 = skip")
     ap.add_argument("--cpu-row-step", type=int, default=8)
     ap.add_argument("--no-value-efficient", action="store_true",
-                    help="N = 1: skip value_efficient (the reference's default renderer: kernels only + `curvis video --mode efficient`)")
+                    help="--full, N = 1: skip value_efficient (the reference's default renderer: kernels only + `curvis video --mode efficient`)")
     ap.add_argument("--value-efficient-frames", type=int, default=0,
                     help="frames of the end-to-end leg of value_efficient (path_orbit.csv resampled to that many frames); 0 = 15 360 "
                          "when /dev/shm has 32 GB free for the 9.5 GB of PNG files and the container's memory limit is above 64 GB (about 1.3 s of rendering: long enough for the binary's fixed "
@@ -103,8 +117,10 @@ def flush_c_stdio():
 
 
 def self_launch(args):
-    """--gpus N > 1 from a plain shell: become `python -m torch.distributed.run --nproc-per-node N bench.py ...`"""
-    # the product's own device count (no `import torch` in a process that is about to exec the launcher: on a box with a cold
+    """--gpus N > 1 from a plain shell: run `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child
+    process and return its exit status (the device count below has initialised the GPU runtime in this process, which
+    must therefore not be replaced by exec)"""
+    # the product's own device count (no `import torch` in a process that only waits for the launcher: on a box with a cold
     # page cache that import alone costs tens of seconds)
     from curvis_amd import _abi
     share = os.environ.get("CURVIS_BENCH_SHARE_DEVICE") == "1"
@@ -121,15 +137,24 @@ def self_launch(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stderr.write("bench.py: no launcher in the environment, starting %d ranks: %s\n" % (args.gpus, " ".join(cmd)))
     sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    proc = subprocess.Popen(cmd)
+    try:
+        rc = proc.wait()
+    except KeyboardInterrupt:
+        proc.terminate()
+        rc = proc.wait()
+    return 128 - rc if rc < 0 else rc  # killed by signal s: the shell's 128 + s
 
 
 def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        self_launch(args)  # does not return
+        sys.exit(self_launch(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -290,12 +315,15 @@ def main():
     timed_clock = {"sclk_mhz_sysfs_before_after": [status_before["sclk_mhz"], status_after["sclk_mhz"]],
                    "power_w_before_after": [status_before["power_w"], status_after["power_w"]]}
     phase("timed_region")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, st, host_frame, args.width, args.height)
+        phase("dump_outputs")
 
     # The reference's output contract: render_image RETURNS an owned host image (src/systems.rs:314-329).  The same
     # launches with the frame copied into page-locked host memory (curvis_host_alloc: one DMA transfer per frame, as
     # `curvis video` does it) -- outside the contract's timed region, reported beside `value`, never as `value`.
     with_download = None
-    if not args.download:
+    if args.full and not args.download:
         hb = curvis_amd.HostBuffer(args.width * args.height * 3)
 
         def step_dl():
@@ -363,7 +391,7 @@ def main():
     # secondary figure, outside the contract's timed region: launches of several frames amortise the ramp and the
     # end-game of a launch (~5 % of a single 1080p frame), which is what a video shard runs as
     multi = None
-    if args.multi_frame > 1 and world == 1:
+    if args.full and args.multi_frame > 1 and world == 1:
         nf = args.multi_frame
         reps = max(2, (args.steps + nf - 1) // nf)
         ctx.render_brute(metric, [cam] * nf, args.max_iter, R, DELTA, download=False)
@@ -388,14 +416,15 @@ def main():
     # power sampled from sysfs while they run -- the chip is power-limited under sustained FP64 load, and boxes differ
     # by a few per cent in the clock they hold; this is where that shows.  Not the contract's `value`.
     sustained = None
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         sustained = sustained_run(ctx, step, args.sustained_seconds, torch)
-    phase("multi_frame_and_sustained")
+    if args.full:
+        phase("multi_frame_and_sustained")
 
     # secondary figure, N > 1: ONE image of the same workload split by rows over the ranks (curvis_render_brute_rows, bit
     # for bit the rows of the whole frame) -- strong scaling of a single image, next to the weak scaling of `value`
     rows_split = None
-    if dist is not None and (world > 1 or os.environ.get("CURVIS_BENCH_FORCE_DIST") == "1") and not args.no_rows_split:
+    if args.full and dist is not None and (world > 1 or os.environ.get("CURVIS_BENCH_FORCE_DIST") == "1") and not args.no_rows_split:
         rows_split = rows_split_run(ctx, dist, torch, world, rank, metric, cam, args, R, DELTA, fence)
         phase("single_image_rows")
 
@@ -449,7 +478,7 @@ def main():
                        "geodesic_relay" if ctx.get_option("last_relay_launches") > 0 else "geodesic_static")
         traffic, traffic_note = pmc_traffic(args, kernel_name)
         being_profiled = any(k in os.environ for k in ("ROCP_TOOL_LIBRARIES", "ROCPROF_OUTPUT_PATH", "ROCPROFILER_LIBRARY_CTOR"))
-        if world == 1 and not args.no_live_traffic and not being_profiled:  # never a profiler inside a profiler
+        if args.full and world == 1 and not args.no_live_traffic and not being_profiled:  # never a profiler inside a profiler
             live_bytes, live = live_traffic(args, kernel_name, per_launch_steps)
             if not isinstance(traffic_note, dict):
                 traffic_note = {}
@@ -466,7 +495,7 @@ def main():
                     traffic_note.update({k: live["sq"][k] for k in ("valu_busy", "valu_instr_per_wave_step", "salu_instr_per_wave_step")})
             else:
                 traffic_note["live"] = {"failed": live}
-        if traffic is None and not args.no_traffic:
+        if traffic is None and args.full and not args.no_traffic:
             raise SystemExit("bench.py: no HBM traffic figure for this workload: %s; live PMC passes: %s (collect a profile "
                              "with tools/gpu_profile_round.sh + tools/make_profiles.py, or pass --no-traffic to report null)"
                              % (traffic_note.get("note"), traffic_note.get("live", "not attempted")))
@@ -570,7 +599,7 @@ def main():
             if sustained is not None:
                 out["value_sustained"]["all_ranks"] = round(sum(r["value_sustained"] or 0.0 for r in per_rank), 1)
         # the reference's DEFAULT renderer (what its CLI runs): secondary figure at N = 1, outside the contract's timed region
-        if dist is None and args.metric == "ellis" and not args.no_value_efficient:
+        if args.full and dist is None and args.metric == "ellis" and not args.no_value_efficient:
             try:
                 out["value_efficient"] = efficient_kernels(ctx, torch, args)
             except Exception as exc:  # noqa: BLE001 -- an extra must never cost the bench line
@@ -578,7 +607,7 @@ def main():
             phase("value_efficient_kernels")
         # the reference's CPU path beside EVERY line (north_star: "timed on the node's own host cores in the same run"):
         # rank 0 runs it after the timed region while the other ranks wait at the barrier below
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             phase("reductions_and_live_pmc_passes")
             out["cpu_baseline"] = cpu_baseline(args, host_skies)
             phase("cpu_baseline")
@@ -591,7 +620,7 @@ def main():
         sky_dev.clear()
     # one visible device per rank (HIP_VISIBLE_DEVICES set by the launcher): rank 0's child would see ONE GPU and
     # `curvis video --devices N` could only fail -- the binary gets the launcher's restriction lifted instead
-    if dist is not None and not args.no_video_e2e and not WEDGED["any"] and (world > 1 or os.environ.get("CURVIS_BENCH_FORCE_DIST") == "1"):
+    if args.full and dist is not None and not args.no_video_e2e and not WEDGED["any"] and (world > 1 or os.environ.get("CURVIS_BENCH_FORCE_DIST") == "1"):
         # the product's own multi-GPU design -- ONE process, N device threads, ncclCommInitAll + curvis_ctx_bcast_skies, shared
         # retry queue, page-locked batch buffers, PNG writer pool -- end to end on a 16N-frame rendition of configs[3]; every
         # rank has released its context, the others wait at the barrier while rank 0 runs the binary over all N GPUs
@@ -663,6 +692,20 @@ def agree(dist, world, ok, why=None):
     dist.all_gather_object(flags, (bool(ok), why))
     bad = ["rank %d: %s" % (r, w) for r, (o, w) in enumerate(flags) if not o]
     return not bad, (bad[0] if bad else None)
+
+
+def dump_outputs(directory, ctx, st, host_frame, width, height):
+    """--dump-outputs: what the last timed step computed, as its caller would receive it -- the frame (read back from HBM,
+    or the page-locked host copy under --download) and the step's counters; the kernel times are left out, they are
+    not results.  1920x1080: 24.9 MB of float32."""
+    os.makedirs(directory, exist_ok=True)
+    if host_frame is not None:
+        frame = np.array(host_frame.array[:width * height * 3]).reshape(height, width, 3)
+    else:
+        frame = ctx.download_frames(width, height, 1)[0]
+    np.save(os.path.join(directory, "frame.npy"), frame.astype(np.float32))
+    counters = [st.rays, st.steps, st.n_pos, st.n_neg, st.n_none, st.n_oob]
+    np.save(os.path.join(directory, "stats.npy"), np.array(counters, dtype=np.float64))
 
 
 def short(exc):

@@ -27,6 +27,17 @@ def test_defaults_follow_the_contract(monkeypatch):
     assert b.FLOP_PER_STEP == {"ellis": 35, "interstellar": 46} and b.ALGO_BYTES_PER_RAY == 7
 
 
+def test_plain_run_is_lean_unless_full(monkeypatch):
+    """the secondary figures are behind --full; --dump-outputs is off unless a directory is given"""
+    b = load_bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out", "--steps", "7"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == "out" and a.steps == 7
+
+
 @pytest.mark.parametrize("extra", [[], ["--gpus", "2"]])
 def test_no_gpu_is_a_loud_failure(extra):
     import torch

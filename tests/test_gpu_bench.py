@@ -64,7 +64,7 @@ def test_two_ranks_sharing_the_device():
     launcher's store, sky distribution (host-staged: RCCL refuses two ranks on one GPU, and the line says that RCCL was not
     used), read-back check on both ranks, barriers, max-over-ranks timing, ONE JSON line carrying n_gpus = 2, the per-rank
     table, cpu_baseline, value_single_image_rows and video_e2e."""
-    r = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--sustained-seconds", "0.5"] + QUICK, {"CURVIS_BENCH_SHARE_DEVICE": "1"})
+    r = run_bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--sustained-seconds", "0.5"] + QUICK, {"CURVIS_BENCH_SHARE_DEVICE": "1"})
     out = the_line(r)
     assert out["n_gpus"] == 2
     check_extras_of_a_multi_rank_line(out, 2, one_device=True)
@@ -81,7 +81,7 @@ def test_two_ranks_agree_on_the_fallback_when_rccl_fails_on_one_of_them():
     """the fall-back is decided TOGETHER.  Two ranks under torchrun (the agent's store: nothing may move
     MASTER_PORT); rank 1 is made to fail before ncclCommInitRank, rank 0 gets out of it by the time limit; both then find
     torch's nccl group unusable (two ranks on one GPU) and both take the host-staged broadcast -- one line, flagged."""
-    r = run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--sustained-seconds", "0", "--no-cpu-baseline", "--no-video-e2e",
+    r = run_bench(["--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--sustained-seconds", "0", "--no-cpu-baseline", "--no-video-e2e",
                    "--no-rows-split", "--multi-frame", "0"] + QUICK,
                   {"CURVIS_BENCH_SHARE_DEVICE": "1", "CURVIS_BENCH_TRY_RCCL": "1", "CURVIS_BENCH_TEST_RCCL_FAIL": "1",
                    "CURVIS_BENCH_RCCL_INIT_TIMEOUT": "8"})
@@ -105,10 +105,33 @@ def test_two_ranks_on_one_gpu_are_refused_without_the_hook():
     assert r.returncode != 0 and r.stdout.strip() == "" and "refusing" in r.stderr
 
 
+def test_plain_line_is_lean_and_dumps_the_last_frame(tmp_path):
+    """a plain run (no --full) times the steps and nothing else; --dump-outputs writes the frame of the last timed step and its
+    counters, which are the oracle's for the same scene"""
+    import numpy as np
+    import oracle_lib as O
+    from curvis_amd import skies
+    W, H = 160, 90
+    r = run_bench(["--steps", "3", "--warmup", "1", "--width", str(W), "--height", str(H), "--sky", "2048",
+                   "--dump-outputs", str(tmp_path)], {})
+    out = the_line(r)
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["metric"].startswith("Mrays/s") and out["unit"].startswith("Mray-steps/s")
+    for extra in ("value_with_download", "value_multi_frame", "value_sustained", "value_efficient", "cpu_baseline", "video_e2e"):
+        assert not out.get(extra), extra
+    frame, stats = np.load(tmp_path / "frame.npy"), np.load(tmp_path / "stats.npy")
+    assert frame.dtype == np.float32 and frame.shape == (H, W, 3) and stats.dtype == np.float64
+    sp, sn = skies.smooth(2048, 1024, 128), skies.smooth(2048, 1024, 32)
+    want, _, st = O.render_image(O.CV, O.ellis(1.0), O.camera(res=(W, H)), O.sky(sp), O.sky(sn), 4096, 100.0, 0.05)
+    assert np.array_equal(frame, want.astype(np.float32))
+    assert stats.tolist() == [st.rays, st.steps, st.n_pos, st.n_neg, st.n_none, st.n_oob]
+    assert out["config"]["executed_steps_per_frame"] == st.steps
+
+
 def test_single_rank_line_carries_sustained_figure_and_device_identity(gpu_ctx):
     st = gpu_ctx.device_status()
     assert len(st["pci_bus_id"].split(":")) == 3          # dddd:bb:dd.f
-    r = run_bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-traffic", "--no-live-traffic", "--multi-frame", "0",
+    r = run_bench(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-traffic", "--no-live-traffic", "--multi-frame", "0",
                    "--sustained-seconds", "1"], {})
     out = the_line(r)
     s = out["value_sustained"]
@@ -123,7 +146,7 @@ def test_single_rank_line_carries_sustained_figure_and_device_identity(gpu_ctx):
 def test_default_line_clock_agrees_with_itself_and_carries_the_download_figure():
     """the clock of the timed region comes from the kernel's own cycle count (live SQ pass / this region's
     kernel time) and must agree with what the 10 s run's sysfs samples say; `value_with_download` is on the default line."""
-    r = run_bench(["--no-cpu-baseline", "--multi-frame", "0", "--sustained-seconds", "4"], {}, timeout=1200)
+    r = run_bench(["--full", "--no-cpu-baseline", "--multi-frame", "0", "--sustained-seconds", "4"], {}, timeout=1200)
     out = the_line(r)
     rf = out["roofline"]
     assert rf["traffic_detail"]["measured_in_this_run"] is True, rf["traffic_detail"].get("live")
@@ -165,7 +188,7 @@ def test_single_rank_over_rccl_takes_the_multi_gpu_code_path():
     """CURVIS_BENCH_FORCE_DIST=1: control plane, the PRODUCT's RCCL path (curvis_rccl_unique_id -> broadcast of the id ->
     curvis_ctx_rccl_comm_init -> curvis_ctx_bcast_skies -> read-back), rows split, `curvis video --devices 1` with its
     single-rank ncclCommInitAll -- the N > 1 code path with the real collective library, on the one GPU a test box has"""
-    r = run_bench(["--steps", "2", "--warmup", "1", "--multi-frame", "0", "--sustained-seconds", "0.5"] + QUICK, {"CURVIS_BENCH_FORCE_DIST": "1"})
+    r = run_bench(["--full", "--steps", "2", "--warmup", "1", "--multi-frame", "0", "--sustained-seconds", "0.5"] + QUICK, {"CURVIS_BENCH_FORCE_DIST": "1"})
     out = the_line(r)                                     # RCCL's banner went to stderr
     assert out["n_gpus"] == 1
     check_extras_of_a_multi_rank_line(out, 1, one_device=True)
@@ -180,7 +203,7 @@ def test_single_rank_over_rccl_takes_the_multi_gpu_code_path():
 def test_rccl_failure_falls_back_and_says_so(inject, backend):
     """a node on which the product's communicator (or RCCL altogether) cannot be brought up must still produce a (flagged)
     line: torch's nccl broadcast, else skies staged through host memory; `collective.fallback_from` says why"""
-    r = run_bench(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-video-e2e", "--no-rows-split", "--multi-frame", "0",
+    r = run_bench(["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-video-e2e", "--no-rows-split", "--multi-frame", "0",
                    "--sustained-seconds", "0"] + QUICK, {"CURVIS_BENCH_FORCE_DIST": "1", "CURVIS_BENCH_TEST_RCCL_FAIL": inject})
     out = the_line(r)
     col = out["collective"]

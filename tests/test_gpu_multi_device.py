@@ -196,7 +196,7 @@ def test_image_rows_over_two_devices_against_oracle(scene_files):
 def test_bench_two_gpus_over_the_products_rccl_path():
     """`bench.py --gpus 2` on two devices: no share hook, the skies through curvis_ctx_bcast_skies, every extra of the N > 1
     line present"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-traffic",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-traffic",
                         "--no-live-traffic", "--sustained-seconds", "1", "--cpu-row-step", "64", "--sky", "2048"],
                        env=clean_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]

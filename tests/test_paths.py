@@ -1,5 +1,8 @@
 """Camera paths of BASELINE configs[3] / [4]: the committed fixtures ARE the reference's files, and the product's own
 closed-form generator (curvis_amd/paths.py) is cross-checked against them."""
+import gzip
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -8,19 +11,25 @@ import pytest
 import refpaths
 from curvis_amd import paths
 
-REF = "/root/reference/paths"
 NAMES = ("path_orbit.csv", "path_through.csv")
+# length, SHA-256 and SHA-512 of the reference's own paths/*.csv, recorded from those files
+REF_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "paths", "reference_files.json")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
 @pytest.mark.parametrize("name", NAMES)
 def test_fixture_is_the_reference_file(name):
-    assert refpaths.reference_path_bytes(name) == open(os.path.join(REF, name), "rb").read()
+    with open(os.path.join(os.path.dirname(refpaths.__file__), "golden", "paths", name + ".gz"), "rb") as f:
+        data = gzip.decompress(f.read())
+    with open(REF_DIGESTS) as f:
+        ref = json.load(f)[name]
+    assert len(data) == ref["bytes"]
+    assert hashlib.sha256(data).hexdigest() == ref["sha256"] and hashlib.sha512(data).hexdigest() == ref["sha512"]
+    assert refpaths.reference_path_bytes(name) == data
 
 
 @pytest.mark.parametrize("name", NAMES)
 def test_fixture_unpacks_to_the_recorded_bytes(name):
-    """runs everywhere (the GPU box has no /root/reference): sha256 of the reference's file, CRLF line ends, 1000 rows x 10"""
+    """sha256 of the reference's file, CRLF line ends, 1000 rows x 10"""
     data = open(refpaths.reference_path_file(name), "rb").read()
     assert data == refpaths.reference_path_bytes(name)      # reference_path_bytes checks the recorded sha256
     assert data.count(b"\r\n") == 1000 and not data.endswith(b"\n")

@@ -96,12 +96,12 @@ def test_wiring_into_the_rendering_settings_reproduces_the_reference_quirks(tmp_
     assert (v.sampling_initial_nums, v.sampling_convergence_threshold_1) == (77, 3e-5)
 
 
-REF_DEFAULTS = "/root/reference/settings/defaults"
+REF_DEFAULTS = os.path.join(ROOT, "tests", "golden", "reference_settings")   # the reference's settings/defaults, byte for byte
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DEFAULTS), reason="the reference tree exists in the build container only")
 def test_reference_default_toml_files_parse_to_the_built_in_defaults(tmp_path):
-    """settings/defaults/*.toml of the reference (what `curvis` falls back to without -c / -s / -i / -v / -m) parse,
+    """settings/defaults/*.toml of the reference (what `curvis` falls back to without -c / -s / -i / -v / -m; committed as
+    data fixtures in tests/golden/reference_settings) parse,
     with this package's reader, to exactly the defaults built into the settings classes -- and the binary's own
     reader accepts the same files"""
     pairs = [("camera_settings.toml", S.CameraSettings), ("simulation_settings.toml", S.SimulationSettings),
