@@ -310,7 +310,8 @@ int prefetch_efficient_impl(curvis_ctx *ctx, const curvis_metric *metric, const 
   if (!metric || !cams || n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
-  if (alpha_nums < 3 || alpha_nums > cvk::kSamplerCap || alpha_nums > cvk::kSamplerPendCap) return CURVIS_OK; /* not a case for the device sampler */
+  /* not a case for the device sampler, or (alpha_nums < 3) one that at most runs one round: the render call samples itself */
+  if (alpha_nums < 3 || alpha_nums > cvk::kSamplerCap || alpha_nums > cvk::kSamplerPendCap) return CURVIS_OK;
   if (!(ctx->device_sampler > 0 || (ctx->device_sampler < 0 && n_frames >= (uint32_t)ctx->device_sampler_min_frames)))
     return CURVIS_OK; /* the render call will take the host-paced sampler: nothing to run ahead */
   for (uint32_t f = 0; f < n_frames; ++f)
@@ -547,7 +548,11 @@ int render_efficient_impl(curvis_ctx *ctx, const curvis_metric *metric, const cu
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   const uint32_t W = cams[0].res_x, H = cams[0].res_y;
   if (W == 0 || H == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
-  if (alpha_nums < 3) return fail(ctx, CURVIS_E_SAMPLING, "alpha_nums < 3: the sampler panics (src/sampling.rs:155-157)");
+  /* compute_uniform_range's `alpha_nums - 1` underflows for 0 (a panic in the reference's default build).  1 and 2 are NOT refused:
+   * the reference panics only inside evaluate_denser_bipoints (src/sampling.rs:155-157), i.e. when a refinement round starts with
+   * fewer than 3 finite samples -- both samplers raise CURVIS_E_SAMPLING there themselves --; with max_iterations_sampling = 0 it
+   * returns a frame from a table of 0, 1 or 2 samples */
+  if (alpha_nums == 0) return fail(ctx, CURVIS_E_SAMPLING, "alpha_nums == 0: compute_uniform_range underflows (src/sampling.rs:133)");
   for (uint32_t f = 0; f < n_frames; ++f) {
     if (cams[f].res_x != W || cams[f].res_y != H)
       return fail(ctx, CURVIS_E_INVALID, "all cameras of a batch must share one resolution");

@@ -216,7 +216,11 @@ int curvis_render_brute_batch(curvis_ctx *ctx, const curvis_metric *metric, cons
  * alpha in [-0.1 pi, 1.1 pi] on the equatorial plane (src/sampling.rs), linear interpolation per pixel
  * (interp 1.0.3), axis-angle rotation of the camera direction, nearest-texel lookup.  Argument names and
  * order are the reference's.  Reproduces the reference's behaviour including the shrinking sample domain
- * (src/sampling.rs:161), extrapolation beyond the last sample and black +/- transitions. */
+ * (src/sampling.rs:161), extrapolation beyond the last sample and black +/- transitions.
+ * CURVIS_E_SAMPLING where the reference panics: alpha_nums == 0 (`alpha_nums - 1` underflows, src/sampling.rs:133), and a
+ * refinement round (max_iterations_sampling > 0) that starts with fewer than 3 finite samples (src/sampling.rs:155-157).
+ * alpha_nums 1 and 2 are accepted: with max_iterations_sampling == 0 the frame is interpolated from a table of 0, 1 or 2
+ * samples, as the reference's is (alpha_nums 1: the one grid point is 0 * inf = NaN, the table empty, every pixel black). */
 int curvis_render_efficient(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *camera,
                             uint32_t max_iterations_propagation, double max_radius, double delta, uint32_t alpha_nums,
                             uint32_t max_iterations_sampling, double sampling_convergence_threshold_1,

@@ -126,6 +126,18 @@ def twin_render_efficient(pm, pc, sky_pos, sky_neg, max_iter, max_radius, delta,
     return rgb, dict(a=a[:k].copy(), e=e[:k].copy(), s=s[:k].copy(), calls=calls.value, steps=steps.value)
 
 
+# Efficient renderer, tables of 0, 1 and 2 samples (max_iterations_sampling = 0: no refinement round, so no "length < 3" panic):
+# (alpha_nums, cap, max_iterations_sampling, samples in the oracle's table) for a camera at l = 5 (Ellis or Interstellar), thresholds
+# 1e-5.  alpha_nums 1: the one grid point is -0.1 pi + 0 * (1.2 pi / 0) = NaN; cap 10: nothing escapes; cap 1925 / 2000: one / two
+# of the three grid points escape in time.  None: a refinement round starts with fewer than 3 finite samples, where the reference
+# panics (src/sampling.rs:155-157).
+EFF_TINY_TABLES = [(2, 4096, 0, 2), (1, 4096, 0, 0), (3, 10, 0, 0), (3, 1925, 0, 1), (3, 2000, 0, 2),
+                   (2, 4096, 1, None), (1, 4096, 1, None), (3, 10, 100, None)]
+# (alpha_nums, max_iterations_sampling) whose uniform grid has points exactly on alpha = 0.0 (37: point 3) or on 0.0 and pi (109:
+# points 9 and 99), unrefined and refined
+EFF_EXACT_GRID = [(37, 0), (37, 37), (109, 0), (109, 109)]
+
+
 def device_count():
     """GPUs the product sees (curvis_device_count; not torch -- importing torch here would bring a second HIP runtime
     into the pytest process)"""

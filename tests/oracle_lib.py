@@ -187,7 +187,7 @@ def render_image_efficient(fl, metric, cam, sky_pos, sky_neg, max_iter, max_radi
     n = smp.n
     samples = dict(a=np.ctypeslib.as_array(smp.a, (n,)).copy(), e=np.ctypeslib.as_array(smp.e, (n,)).copy(),
                    s=np.ctypeslib.as_array(smp.s, (n,)).copy(), calls=smp.calls, steps=smp.steps,
-                   rounds=smp.rounds)
+                   rounds=smp.rounds, warned_max_iterations=smp.warned_max_iterations)
     lib().cvo_samples_free(C.byref(smp))
     return rgb, samples, st
 

@@ -59,20 +59,60 @@ def test_device_sampler_control_flow_equals_the_host_sampler_on_hard_settings():
              ("interstellar", -3.0, 8192, 50, 100, 1e-6, 1e-5), ("ellis", 40.0, 4096, 100, 100, 1e-5, 1e-5)]
     overflowed = 0
     for metric, l, cap, n0, maxit, t1, t2 in cases:
-        _, _, pm, pc = common.scene(metric, res=(6, 4), pos=(0.0, l, common.HALF_PI, 0.3))
-        res = []
-        for dev in (0, 1, 2):
-            try:
-                rgb, got = common.twin_render_efficient(pm, pc, sp, sn, cap, 100.0, 0.05, n0, maxit, t1, t2, fast=1, dev_sampler=dev)
-                res.append((rgb.tobytes(), got["calls"], got["steps"]) + tuple(got[k].tobytes() for k in "aes"))
-            except RuntimeError as exc:
-                res.append(str(exc))
+        om, oc, pm, pc = common.scene(metric, res=(6, 4), pos=(0.0, l, common.HALF_PI, 0.3))
+        want = _oracle_outcome(om, oc, sp, sn, cap, n0, maxit, t1, t2)
+        res = [_twin_outcome(pm, pc, sp, sn, cap, n0, maxit, t1, t2, dev) for dev in (0, 1, 2)]
+        assert res[0] == want, (metric, l, cap, n0, maxit, t1, t2)
         if res[1] == "twin efficient render failed: -4":   # the fixed arrays ran out (the product then falls back to the host sampler)
             assert len(res[0][3]) // 8 > 700 and res[2] == res[1], (metric, l, n0, t1)     # ... which may only happen to tables that really are large
             overflowed += 1
             continue
         assert res[0] == res[1] == res[2], (metric, l, cap, n0, maxit, t1, t2)
     assert overflowed == 1
+
+
+def _oracle_outcome(om, oc, sp, sn, cap, n0, maxit, t1, t2):
+    """what _twin_outcome returns, from the oracle (CVO_CV): the frame and the table, or "panic" """
+    try:
+        rgb, want, _ = O.render_image_efficient(O.CV, om, oc, O.sky(sp), O.sky(sn), cap, 100.0, 0.05, n0, maxit, t1, t2)
+    except RuntimeError:
+        return "panic"
+    return (rgb.tobytes(), want["calls"], want["steps"]) + tuple(want[k].tobytes() for k in "aes")
+
+
+def _twin_outcome(pm, pc, sp, sn, cap, n0, maxit, t1, t2, dev):
+    try:
+        rgb, got = common.twin_render_efficient(pm, pc, sp, sn, cap, 100.0, 0.05, n0, maxit, t1, t2, fast=1, dev_sampler=dev)
+    except RuntimeError as exc:
+        return "panic" if str(exc) == "twin efficient render failed: -2" else str(exc)
+    return (rgb.tobytes(), got["calls"], got["steps"]) + tuple(got[k].tobytes() for k in "aes")
+
+
+@pytest.mark.parametrize("metric", ["ellis", "interstellar"])
+def test_tiny_tables_equal_the_oracle(metric):
+    """every sampler (host, device control flow with and without speculation) against the oracle on tables of 0, 1 and 2 samples
+    and on the rows where the oracle panics; the frame is 16 x 10 so that the optical-axis pixel (alpha = 0, NaN rotation axis)
+    is one of them"""
+    sp, sn = common.make_skies(64, 32, "check")
+    om, oc, pm, pc = common.scene(metric, res=(16, 10))
+    for n0, cap, maxit, n_want in common.EFF_TINY_TABLES:
+        want = _oracle_outcome(om, oc, sp, sn, cap, n0, maxit, 1e-5, 1e-5)
+        assert (want == "panic") if n_want is None else (len(want[3]) // 8 == n_want), (n0, cap, maxit)
+        for dev in (0, 1, 2):
+            assert _twin_outcome(pm, pc, sp, sn, cap, n0, maxit, 1e-5, 1e-5, dev) == want, (n0, cap, maxit, dev)
+
+
+def test_grid_points_exactly_on_zero_and_pi_equal_the_oracle():
+    """n0 = 37 / 109 put grid points exactly on alpha = 0.0 / 0.0 and pi: pixel queries (the optical axis: alpha = 0) hit a sample
+    abscissa exactly, and refinement takes midpoints on either side of it"""
+    sp, sn = common.make_skies(64, 32, "check")
+    om, oc, pm, pc = common.scene("ellis", res=(16, 10))
+    for n0, maxit in common.EFF_EXACT_GRID:
+        want = _oracle_outcome(om, oc, sp, sn, 4096, n0, maxit, 1e-5, 1e-5)
+        a = np.frombuffer(want[3], np.float64)
+        assert 0.0 in a and (np.pi in a) == (n0 == 109), n0
+        for dev in (0, 1, 2):
+            assert _twin_outcome(pm, pc, sp, sn, 4096, n0, maxit, 1e-5, 1e-5, dev) == want, (n0, maxit, dev)
 
 
 def test_bucket_grid_lookup_equals_the_full_search():

@@ -90,15 +90,22 @@ def test_gpu_reproduces_brute_fixtures(gpu_ctx, name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(G.EFFICIENT))
 def test_gpu_reproduces_efficient_fixtures(gpu_ctx, name):
+    """on the host-paced sampler and on the device-resident one (forced: a single frame takes the host-paced one by default)"""
     metric, res, pos, fwd, cap = G.EFFICIENT[name]
     g = load(name)
     sp, sn = common.make_skies(*G.SKY, "check")
     _, _, pm, pc = common.scene(metric, res=res, pos=pos, fwd=fwd)
     sys_ = curvis_amd.RelativisticSystem(pm, curvis_amd.SphericalImage(sp), curvis_amd.SphericalImage(sn), pc,
                                          context=gpu_ctx)
-    rgb = sys_.render_image_efficient(cap, 100.0, 0.05, 100, 100, 1e-5, 1e-5)
-    a, e, s = gpu_ctx.samples(0)
-    assert np.array_equal(rgb, g["rgb_cv"])
-    assert np.array_equal(common.bits(a), common.bits(g["a_cv"])) and np.array_equal(common.bits(e), common.bits(g["e_cv"]))
-    assert np.array_equal(s, g["s_cv"])
-    assert np.array_equal(rgb, g["rgb_libm"])   # pixel-identical to the glibc flavour (measured)
+    for device_sampler in (0, 1):
+        try:
+            gpu_ctx.set_option("device_sampler", device_sampler)
+            rgb = sys_.render_image_efficient(cap, 100.0, 0.05, 100, 100, 1e-5, 1e-5)
+            assert gpu_ctx.get_option("last_sampler_path") == device_sampler
+            a, e, s = gpu_ctx.samples(0)
+        finally:
+            gpu_ctx.set_option("device_sampler", -1)
+        assert np.array_equal(rgb, g["rgb_cv"]), device_sampler
+        assert np.array_equal(common.bits(a), common.bits(g["a_cv"])) and np.array_equal(common.bits(e), common.bits(g["e_cv"])), device_sampler
+        assert np.array_equal(s, g["s_cv"]), device_sampler
+        assert np.array_equal(rgb, g["rgb_libm"]), device_sampler   # pixel-identical to the glibc flavour (measured)

@@ -271,24 +271,33 @@ EFF_CASES = [
 @pytest.mark.parametrize("metric,res,pos,fwd,cap,n0", EFF_CASES)
 def test_efficient_mode_bit_exact_vs_oracle(gpu_ctx, fast, metric, res, pos, fwd, cap, n0):
     """render_image_efficient (what `curvis image` / `curvis video` call): the adaptive sample table
-    (alphas, escape angles, escape spaces), the sampler bookkeeping and every pixel, bit for bit."""
+    (alphas, escape angles, escape spaces), the sampler bookkeeping and every pixel, bit for bit -- on the host-paced
+    sampler and on the device-resident one (a single frame takes the host-paced one unless the option forces it),
+    both against the same oracle frame."""
     sp, sn = common.make_skies(512, 256, "check")
     om, oc, pm, pc = common.scene(metric, res=res, pos=pos, fwd=fwd)
     want_rgb, want, st = O.render_image_efficient(O.CV, om, oc, O.sky(sp), O.sky(sn), cap, 100.0, 0.05, n0, n0, 1e-5,
                                                   1e-5)
-    gpu_ctx.set_option("fast_math", fast)
     sys_ = curvis_amd.RelativisticSystem(pm, curvis_amd.SphericalImage(sp), curvis_amd.SphericalImage(sn), pc,
                                          context=gpu_ctx)
-    got_rgb = sys_.render_image_efficient(cap, 100.0, 0.05, n0, n0, 1e-5, 1e-5)
-    a, e, s = gpu_ctx.samples(0)
-    info = gpu_ctx.sampling_info(0)
-    gpu_ctx.set_option("fast_math", 1)
-    assert (info.n_samples, info.calls, info.steps) == (len(want["a"]), want["calls"], want["steps"])
-    assert np.array_equal(common.bits(a), common.bits(want["a"]))
-    assert np.array_equal(common.bits(e), common.bits(want["e"]))
-    assert np.array_equal(common.bits(s), common.bits(want["s"]))
-    assert np.array_equal(got_rgb, want_rgb)
-    assert sys_.last_stats.steps == want["steps"]
+    for device_sampler in (0, 1):
+        try:
+            gpu_ctx.set_option("fast_math", fast)
+            gpu_ctx.set_option("device_sampler", device_sampler)
+            got_rgb = sys_.render_image_efficient(cap, 100.0, 0.05, n0, n0, 1e-5, 1e-5)
+            assert gpu_ctx.get_option("last_sampler_path") == device_sampler
+            a, e, s = gpu_ctx.samples(0)
+            info = gpu_ctx.sampling_info(0)
+        finally:
+            gpu_ctx.set_option("fast_math", 1)
+            gpu_ctx.set_option("device_sampler", -1)
+        assert (info.n_samples, info.calls, info.steps) == (len(want["a"]), want["calls"], want["steps"]), device_sampler
+        assert (info.rounds, info.warned_max_iterations) == (want["rounds"], want["warned_max_iterations"]), device_sampler
+        assert np.array_equal(common.bits(a), common.bits(want["a"])), device_sampler
+        assert np.array_equal(common.bits(e), common.bits(want["e"])), device_sampler
+        assert np.array_equal(common.bits(s), common.bits(want["s"])), device_sampler
+        assert np.array_equal(got_rgb, want_rgb), device_sampler
+        assert sys_.last_stats.steps == want["steps"], device_sampler
 
 
 def test_efficient_batch_equals_single_frames(gpu_ctx):
@@ -318,15 +327,24 @@ def test_efficient_default_960x540_vs_oracle(gpu_ctx):
                                                   1e-5, 1e-5)
     sys_ = curvis_amd.RelativisticSystem(pm, curvis_amd.SphericalImage(sp), curvis_amd.SphericalImage(sn), pc,
                                          context=gpu_ctx)
-    got = sys_.render_image_efficient(40000, 100.0, 0.05, 100, 100, 1e-5, 1e-5)
-    assert np.array_equal(got, want_rgb)
+    got = {}
+    try:
+        for device_sampler in (0, 1):   # the host-paced sampler and the device-resident one, against the same oracle frames
+            gpu_ctx.set_option("device_sampler", device_sampler)
+            got[device_sampler] = sys_.render_image_efficient(40000, 100.0, 0.05, 100, 100, 1e-5, 1e-5)
+            assert gpu_ctx.get_option("last_sampler_path") == device_sampler
+            assert np.array_equal(got[device_sampler], want_rgb), device_sampler
+    finally:
+        gpu_ctx.set_option("device_sampler", -1)
     # against the three glibc flavours (what a Linux build of the reference computes, with or without sincos merging)
     for fl in O.GLIBC_FLAVOURS:
         libm_rgb, _, _ = O.render_image_efficient(fl, om, oc, O.sky(sp), O.sky(sn), 40000, 100.0, 0.05, 100, 100, 1e-5,
                                                   1e-5)
-        d = np.abs(got.astype(int) - libm_rgb.astype(int)).max(axis=2)
-        print("efficient 960x540 vs %s: exact %.5f, <=1 LSB %.5f, max %d" % (O.FLAVOUR_NAMES[fl], (d == 0).mean(), (d <= 1).mean(), d.max()))
-        assert d.max() == 0, O.FLAVOUR_NAMES[fl]  # measured: 518 400 of 518 400 pixels identical (profiles/round3_libm_parity.txt)
+        for device_sampler, img in got.items():
+            d = np.abs(img.astype(int) - libm_rgb.astype(int)).max(axis=2)
+            print("efficient 960x540 (device_sampler %d) vs %s: exact %.5f, <=1 LSB %.5f, max %d" % (
+                device_sampler, O.FLAVOUR_NAMES[fl], (d == 0).mean(), (d <= 1).mean(), d.max()))
+            assert d.max() == 0, O.FLAVOUR_NAMES[fl]  # measured: 518 400 of 518 400 pixels identical (profiles/round3_libm_parity.txt)
 
 
 def config3_oracle_frame(threads=None):
