@@ -3,10 +3,14 @@
  * Pieces (each included here and nowhere else; `make asm` before/after the split: the same instructions):
  *   kernels_geodesic.h   device side of RelativisticSystem::render_image (src/systems.rs:307-330, rows R1-R10 of SURVEY.md 8a)
  *   kernels_efficient.h  device side of render_image_efficient (src/systems.rs:333-527), direct mode, trajectories, math self-test
- *   render_host.h        struct curvis_ctx, kernel selection, render_impl, per-frame statistics, the relay seat belt
- *   efficient_host.h     the adaptive sampler's driver (src/sampling.rs) over batched escape-angle launches, per-pixel launch
+ *   hip_owned.h          the owners of the HIP resources (device / page-locked buffers, events, streams, sky textures): what a
+ *                        context or a call holds is freed by destructors, on every return path
+ *   render_host.h        struct curvis_ctx, with_kind / with_flag (metric kind and step flavour -> template arguments), kernel
+ *                        selection, render_impl = path decision + render_chunk + relay_seat_belt, per-frame statistics
+ *   efficient_host.h     the adaptive sampler's driver (src/sampling.rs) over batched escape-angle launches, the device sampler's
+ *                        slots and prefetch, per-pixel launch and statistics shared by the two
  *   kernels_png.h, png_host.h   PNG front end on the device: the frames in HBM -> one zlib stream per frame (src/rendering.rs:110, :311)
- *   (this file)          the extern "C" entry points
+ *   (this file)          the extern "C" entry points; kOptions, the one table of option keys behind set_option / get_option
  *   per-ray arithmetic: cv_device.h / cv_efficient.h / cv_sampler.h / cv_math.h (shared with the host twin of the tests)
  *
  * Kernels
@@ -51,6 +55,7 @@
 #include <atomic>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <rccl/rccl.h>
@@ -68,6 +73,7 @@
 
 #include "kernels_geodesic.h"
 #include "kernels_efficient.h"
+#include "hip_owned.h"
 #include "render_host.h"
 #include "efficient_host.h"
 #include "png_codes.h"
@@ -101,24 +107,18 @@ int curvis_ctx_create(int device, curvis_ctx **out) {
   ctx->device = device;
   for (int s = 0; s < 2; ++s)
     for (int i = 0; i < 9; ++i) ctx->sky_inv_rot[s][i] = (i % 4 == 0) ? 1.0 : 0.0;
-  auto bail = [&](const std::string &m) {
+  auto bail = [&](int code, const std::string &m) {
     g_create_error = m;
     curvis_ctx_destroy(ctx);
-    return CURVIS_E_HIP;
+    return code;
   };
-  if ((e = hipSetDevice(device)) != hipSuccess) return bail(std::string("hipSetDevice: ") + hipGetErrorString(e));
+  if ((e = hipSetDevice(device)) != hipSuccess) return bail(CURVIS_E_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e));
   if ((e = hipGetDeviceProperties(&ctx->prop, device)) != hipSuccess)
-    return bail(std::string("hipGetDeviceProperties: ") + hipGetErrorString(e));
-  if (std::strncmp(ctx->prop.gcnArchName, "gfx950", 6) != 0) {
-    g_create_error = std::string("device is ") + ctx->prop.gcnArchName + ", this library carries gfx950 code only";
-    curvis_ctx_destroy(ctx);
-    return CURVIS_E_NO_DEVICE;
-  }
-  if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess)
-    return bail(std::string("hipStreamCreate: ") + hipGetErrorString(e));
-  if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess || (e = hipEventCreate(&ctx->ev1)) != hipSuccess ||
-      (e = hipEventCreate(&ctx->ev2)) != hipSuccess)
-    return bail(std::string("hipEventCreate: ") + hipGetErrorString(e));
+    return bail(CURVIS_E_HIP, std::string("hipGetDeviceProperties: ") + hipGetErrorString(e));
+  if (std::strncmp(ctx->prop.gcnArchName, "gfx950", 6) != 0)
+    return bail(CURVIS_E_NO_DEVICE, std::string("device is ") + ctx->prop.gcnArchName + ", this library carries gfx950 code only");
+  if (ctx->stream.ensure(ctx, hipStreamNonBlocking) || ctx->ev0.ensure(ctx) || ctx->ev1.ensure(ctx) || ctx->ev2.ensure(ctx))
+    return bail(CURVIS_E_HIP, std::string(ctx->err)); /* (a copy: bail deletes the context) */
   *out = ctx;
   return CURVIS_OK;
 }
@@ -126,40 +126,10 @@ int curvis_ctx_create(int device, curvis_ctx **out) {
 void curvis_ctx_destroy(curvis_ctx *ctx) {
   if (!ctx) return;
   if (ctx->device >= 0) (void)hipSetDevice(ctx->device);
+  /* these three waits are what makes the order in which the members' destructors free things immaterial: nothing is in flight */
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream); /* a download still in flight reads d_fb / d_fb_alt */
   if (ctx->sampler_stream) (void)hipStreamSynchronize(ctx->sampler_stream); /* a prefetched sampler still writes its slot */
-  for (auto &S : ctx->samp) {
-    if (S.d) (void)hipFree(S.d);
-    if (S.h) (void)hipHostFree(S.h);
-    if (S.done) (void)hipEventDestroy(S.done);
-    if (S.t0) (void)hipEventDestroy(S.t0);
-    if (S.t1) (void)hipEventDestroy(S.t1);
-  }
-  if (ctx->sampler_stream) (void)hipStreamDestroy(ctx->sampler_stream);
-  for (int s = 0; s < 2; ++s)
-    if (ctx->d_sky[s] && ctx->sky_owned[s]) (void)hipFree(ctx->d_sky[s]);
-  if (ctx->d_fb) (void)hipFree(ctx->d_fb);
-  if (ctx->d_fb_alt) (void)hipFree(ctx->d_fb_alt);
-  if (ctx->ev_fb) (void)hipEventDestroy(ctx->ev_fb);
-  if (ctx->ev_dl) (void)hipEventDestroy(ctx->ev_dl);
-  if (ctx->ev_streams) (void)hipEventDestroy(ctx->ev_streams);
-  if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-  if (ctx->d_dbg) (void)hipFree(ctx->d_dbg);
-  if (ctx->d_store) (void)hipFree(ctx->d_store);
-  if (ctx->d_rq) (void)hipFree(ctx->d_rq);
-  if (ctx->d_verify) (void)hipFree(ctx->d_verify);
-  if (ctx->d_png) (void)hipFree(ctx->d_png);
-  if (ctx->d_eff) (void)hipFree(ctx->d_eff);
-  if (ctx->h_eff) (void)hipHostFree(ctx->h_eff);
-  if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
-  if (ctx->d_cams) (void)hipFree(ctx->d_cams);
-  if (ctx->h_cams) (void)hipHostFree(ctx->h_cams);
-  if (ctx->d_counters) (void)hipFree(ctx->d_counters);
-  if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
-  if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
 
@@ -241,22 +211,16 @@ static int set_sky_common(curvis_ctx *ctx, int which, uint32_t w, uint32_t h) {
   if (which < 0 || which > 1) return fail(ctx, CURVIS_E_INVALID, "which must be 0 (+l) or 1 (-l)");
   if (w == 0 || h == 0) return fail(ctx, CURVIS_E_INVALID, "empty sky image");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (ctx->d_sky[which] && ctx->sky_owned[which]) HIP_TRY(ctx, hipFree(ctx->d_sky[which]));
-  ctx->d_sky[which] = nullptr;
-  ctx->sky_owned[which] = false;
-  ctx->sky_w[which] = w;
-  ctx->sky_h[which] = h;
-  return CURVIS_OK;
+  return ctx->sky[which].reset(ctx, w, h);
 }
 
 int curvis_ctx_set_sky(curvis_ctx *ctx, int which, const uint8_t *rgba, uint32_t w, uint32_t h) {
   int rc = set_sky_common(ctx, which, w, h);
   if (rc) return rc;
-  const size_t bytes = (size_t)w * h * 4;
-  HIP_TRY(ctx, hipMalloc(&ctx->d_sky[which], bytes));
-  ctx->sky_owned[which] = true;
+  SkyTexture &S = ctx->sky[which];
+  if ((rc = S.allocate(ctx))) return rc;
   if (rgba) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sky[which], rgba, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(S.texels, rgba, S.bytes(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return CURVIS_OK;
@@ -266,16 +230,14 @@ int curvis_ctx_set_sky_device(curvis_ctx *ctx, int which, const void *dev_rgba, 
   if (!dev_rgba) return fail(ctx, CURVIS_E_INVALID, "null device pointer");
   int rc = set_sky_common(ctx, which, w, h);
   if (rc) return rc;
-  const size_t bytes = (size_t)w * h * 4;
-  if (copy) {
-    HIP_TRY(ctx, hipMalloc(&ctx->d_sky[which], bytes));
-    ctx->sky_owned[which] = true;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sky[which], dev_rgba, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  } else {
-    ctx->d_sky[which] = const_cast<void *>(dev_rgba);
-    ctx->sky_owned[which] = false;
+  SkyTexture &S = ctx->sky[which];
+  if (!copy) {
+    S.borrow(dev_rgba);
+    return CURVIS_OK;
   }
+  if ((rc = S.allocate(ctx))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(S.texels, dev_rgba, S.bytes(), hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return CURVIS_OK;
 }
 
@@ -321,25 +283,22 @@ int curvis_ctx_bcast_skies(curvis_ctx *ctx, void *nccl_comm, int root) {
   /* header first: {root_ok, w0, h0, w1, h1}, then the two textures.  root_ok travels with the shapes so that a
    * root without skies makes EVERY rank return CURVIS_E_NO_SKY together -- a root that returned before the
    * collective would leave its peers waiting inside ncclBroadcast for ever. */
-  uint32_t *d_hdr = nullptr;
-  HIP_TRY(ctx, hipMalloc((void **)&d_hdr, 5 * sizeof(uint32_t)));
-  uint32_t hdr[5] = {0u, ctx->sky_w[0], ctx->sky_h[0], ctx->sky_w[1], ctx->sky_h[1]};
+  DeviceBuffer<uint32_t> d_hdr; /* freed on every return below */
+  int rc = d_hdr.reserve(ctx, 5);
+  if (rc) return rc;
+  uint32_t hdr[5] = {0u, ctx->sky[0].w, ctx->sky[0].h, ctx->sky[1].w, ctx->sky[1].h};
   if (rank == root) {
-    hdr[0] = (ctx->d_sky[0] && ctx->d_sky[1]) ? 1u : 0u;
+    hdr[0] = (ctx->sky[0].texels && ctx->sky[1].texels) ? 1u : 0u;
     HIP_TRY(ctx, hipMemcpyAsync(d_hdr, hdr, sizeof hdr, hipMemcpyHostToDevice, ctx->stream));
   }
-  nrc = ncclBroadcast(d_hdr, d_hdr, 5, ncclUint32, root, comm, ctx->stream);
-  if (nrc != ncclSuccess) {
-    (void)hipFree(d_hdr);
+  nrc = ncclBroadcast(d_hdr.p, d_hdr.p, 5, ncclUint32, root, comm, ctx->stream);
+  if (nrc != ncclSuccess)
     return fail(ctx, CURVIS_E_RCCL, "sky broadcast, stage header_broadcast: ncclBroadcast: " + rccl_detail(comm, nrc));
-  }
-  int rc = bcast_stage_sync(ctx, comm, "header_broadcast");
-  if (rc == CURVIS_OK) {
-    const hipError_t e = hipMemcpy(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(ctx, CURVIS_E_HIP, std::string("sky broadcast, stage header_broadcast: reading the header back: ") + hipGetErrorString(e));
-  }
-  (void)hipFree(d_hdr);
+  rc = bcast_stage_sync(ctx, comm, "header_broadcast");
   if (rc != CURVIS_OK) return rc;
+  const hipError_t e = hipMemcpy(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost);
+  if (e != hipSuccess)
+    return fail(ctx, CURVIS_E_HIP, std::string("sky broadcast, stage header_broadcast: reading the header back: ") + hipGetErrorString(e));
   if (hdr[0] != 1u)
     return fail(ctx, CURVIS_E_NO_SKY, rank == root ? "root rank must hold both skies before the broadcast"
                                                    : "the root rank of the sky broadcast holds no skies");
@@ -351,7 +310,7 @@ int curvis_ctx_bcast_skies(curvis_ctx *ctx, void *nccl_comm, int root) {
       rc = curvis_ctx_set_sky(ctx, s, nullptr, w, h);
       if (rc) return fail(ctx, rc, std::string("sky broadcast, stage ") + stage + ": allocating the receiving texture: " + ctx->err);
     }
-    nrc = ncclBroadcast(ctx->d_sky[s], ctx->d_sky[s], (size_t)w * h * 4, ncclUint8, root, comm, ctx->stream);
+    nrc = ncclBroadcast(ctx->sky[s].texels, ctx->sky[s].texels, (size_t)w * h * 4, ncclUint8, root, comm, ctx->stream);
     if (nrc != ncclSuccess)
       return fail(ctx, CURVIS_E_RCCL, std::string("sky broadcast, stage ") + stage + ": ncclBroadcast: " + rccl_detail(comm, nrc));
     rc = bcast_stage_sync(ctx, comm, stage); /* one synchronisation per texture: the error names the texture */
@@ -431,12 +390,12 @@ int curvis_rccl_comm_destroy(void *nccl_comm) {
 
 int curvis_ctx_read_sky(curvis_ctx *ctx, int which, size_t offset, size_t bytes, uint8_t *out) {
   if (!ctx || !out || which < 0 || which > 1) return fail(ctx, CURVIS_E_INVALID, "bad argument");
-  if (!ctx->d_sky[which]) return fail(ctx, CURVIS_E_NO_SKY, "sky not set");
-  const size_t total = (size_t)ctx->sky_w[which] * ctx->sky_h[which] * 4;
+  if (!ctx->sky[which].texels) return fail(ctx, CURVIS_E_NO_SKY, "sky not set");
+  const size_t total = ctx->sky[which].bytes();
   if (offset > total || bytes > total - offset) return fail(ctx, CURVIS_E_INVALID, "range outside the texture");
   if (bytes == 0) return CURVIS_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(out, (const uint8_t *)ctx->d_sky[which] + offset, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(out, (const uint8_t *)ctx->sky[which].texels + offset, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return CURVIS_OK;
 }
@@ -497,11 +456,7 @@ int curvis_metric_functions(const curvis_metric *m, double l, double *r, double 
   if (curvis_metric_validate(m) != CURVIS_OK) return CURVIS_E_METRIC;
   const cvk::MetricParams MP = make_metric(*m);
   double rr, r2, rd;
-  switch (m->kind) {
-    case CURVIS_METRIC_ELLIS: cvk::metric_eval<cvk::METRIC_ELLIS>(MP, l, rr, r2, rd); break;
-    case CURVIS_METRIC_INTERSTELLAR: cvk::metric_eval<cvk::METRIC_INTERSTELLAR>(MP, l, rr, r2, rd); break;
-    default: cvk::metric_eval<cvk::METRIC_FLAT>(MP, l, rr, r2, rd); break;
-  }
+  with_kind(m->kind, [&](auto K) { cvk::metric_eval<decltype(K)::value>(MP, l, rr, r2, rd); });
   if (r) *r = rr;
   if (r_squared) *r_squared = r2;
   if (r_derivative) *r_derivative = rd;
@@ -557,13 +512,7 @@ int curvis_vector_to_direction(const curvis_metric *metric, const double positio
   q.p2 = p_cov[2];
   q.p3 = p_cov[3];
   q.p3sq = q.p3 * q.p3;
-  switch (metric->kind) {
-    case CURVIS_METRIC_ELLIS: cvk::ray_direction<cvk::METRIC_ELLIS>(MP, q, direction[0], direction[1], direction[2]); break;
-    case CURVIS_METRIC_INTERSTELLAR:
-      cvk::ray_direction<cvk::METRIC_INTERSTELLAR>(MP, q, direction[0], direction[1], direction[2]);
-      break;
-    default: cvk::ray_direction<cvk::METRIC_FLAT>(MP, q, direction[0], direction[1], direction[2]); break;
-  }
+  with_kind(metric->kind, [&](auto K) { cvk::ray_direction<decltype(K)::value>(MP, q, direction[0], direction[1], direction[2]); });
   return CURVIS_OK;
 }
 
@@ -571,11 +520,7 @@ int curvis_update_relativistic_object(const curvis_metric *metric, double x[4], 
   if (!metric || !x || !p_cov) return CURVIS_E_INVALID;
   if (curvis_metric_validate(metric) != CURVIS_OK) return CURVIS_E_METRIC;
   const cvk::MetricParams MP = make_metric(*metric);
-  switch (metric->kind) {
-    case CURVIS_METRIC_ELLIS: host_euler_step<cvk::METRIC_ELLIS>(MP, x, p_cov, delta); break;
-    case CURVIS_METRIC_INTERSTELLAR: host_euler_step<cvk::METRIC_INTERSTELLAR>(MP, x, p_cov, delta); break;
-    default: host_euler_step<cvk::METRIC_FLAT>(MP, x, p_cov, delta); break;
-  }
+  with_kind(metric->kind, [&](auto K) { host_euler_step<decltype(K)::value>(MP, x, p_cov, delta); });
   return CURVIS_OK;
 }
 
@@ -624,9 +569,9 @@ int curvis_render_efficient(curvis_ctx *ctx, const curvis_metric *metric, const 
                             uint32_t max_iterations_propagation, double max_radius, double delta, uint32_t alpha_nums,
                             uint32_t max_iterations_sampling, double sampling_convergence_threshold_1,
                             double sampling_convergence_threshold_2, uint8_t *rgb_out, curvis_stats *stats) {
-  return render_efficient_impl(ctx, metric, camera, 1, max_iterations_propagation, max_radius, delta, alpha_nums,
-                               max_iterations_sampling, sampling_convergence_threshold_1,
-                               sampling_convergence_threshold_2, rgb_out, stats);
+  const EfficientCall call = {metric, camera, 1, max_iterations_propagation, max_radius, delta, alpha_nums, max_iterations_sampling,
+                              sampling_convergence_threshold_1, sampling_convergence_threshold_2};
+  return render_efficient_impl(ctx, call, rgb_out, stats);
 }
 
 int curvis_render_efficient_batch(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cameras,
@@ -634,17 +579,18 @@ int curvis_render_efficient_batch(curvis_ctx *ctx, const curvis_metric *metric, 
                                   double delta, uint32_t alpha_nums, uint32_t max_iterations_sampling,
                                   double sampling_convergence_threshold_1, double sampling_convergence_threshold_2,
                                   uint8_t *rgb_out, curvis_stats *stats) {
-  return render_efficient_impl(ctx, metric, cameras, n_frames, max_iterations_propagation, max_radius, delta,
-                               alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
-                               sampling_convergence_threshold_2, rgb_out, stats);
+  const EfficientCall call = {metric, cameras, n_frames, max_iterations_propagation, max_radius, delta, alpha_nums, max_iterations_sampling,
+                              sampling_convergence_threshold_1, sampling_convergence_threshold_2};
+  return render_efficient_impl(ctx, call, rgb_out, stats);
 }
 
 int curvis_ctx_prefetch_efficient(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cameras, uint32_t n_frames,
                                   uint32_t max_iterations_propagation, double max_radius, double delta, uint32_t alpha_nums,
                                   uint32_t max_iterations_sampling, double sampling_convergence_threshold_1,
                                   double sampling_convergence_threshold_2) {
-  return prefetch_efficient_impl(ctx, metric, cameras, n_frames, max_iterations_propagation, max_radius, delta, alpha_nums,
-                                 max_iterations_sampling, sampling_convergence_threshold_1, sampling_convergence_threshold_2);
+  const EfficientCall call = {metric, cameras, n_frames, max_iterations_propagation, max_radius, delta, alpha_nums, max_iterations_sampling,
+                              sampling_convergence_threshold_1, sampling_convergence_threshold_2};
+  return prefetch_efficient_impl(ctx, call);
 }
 
 int curvis_render_direct(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *camera, uint32_t max_iterations,
@@ -687,17 +633,7 @@ int curvis_new_photon(const curvis_metric *metric, const double position[4], con
   if (curvis_metric_validate(metric) != CURVIS_OK) return CURVIS_E_METRIC;
   const cvk::MetricParams MP = make_metric(*metric);
   cvk::Ray q;
-  switch (metric->kind) {
-    case CURVIS_METRIC_ELLIS:
-      cvk::ray_init_dir<cvk::METRIC_ELLIS>(MP, position, direction[0], direction[1], direction[2], q);
-      break;
-    case CURVIS_METRIC_INTERSTELLAR:
-      cvk::ray_init_dir<cvk::METRIC_INTERSTELLAR>(MP, position, direction[0], direction[1], direction[2], q);
-      break;
-    default:
-      cvk::ray_init_dir<cvk::METRIC_FLAT>(MP, position, direction[0], direction[1], direction[2], q);
-      break;
-  }
+  with_kind(metric->kind, [&](auto K) { cvk::ray_init_dir<decltype(K)::value>(MP, position, direction[0], direction[1], direction[2], q); });
   for (int i = 0; i < 4; ++i) x[i] = position[i];
   p_cov[0] = 1.0;
   p_cov[1] = q.p1;
@@ -715,9 +651,9 @@ int curvis_photon_trajectories(curvis_ctx *ctx, const curvis_metric *metric, uin
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t in_bytes = (size_t)n_photons * 4 * sizeof(double);
   const size_t out_bytes = (size_t)n_photons * iterations * 8 * sizeof(double);
-  int rc = ensure_device(ctx, ctx->d_eff, ctx->eff_cap, 2 * in_bytes + out_bytes);
+  int rc = ctx->d_eff.reserve(ctx, 2 * in_bytes + out_bytes);
   if (rc) return rc;
-  double *d_x = (double *)ctx->d_eff, *d_p = d_x + (size_t)n_photons * 4, *d_out = d_p + (size_t)n_photons * 4;
+  double *d_x = (double *)ctx->d_eff.p, *d_p = d_x + (size_t)n_photons * 4, *d_out = d_p + (size_t)n_photons * 4;
   HIP_TRY(ctx, hipMemcpyAsync(d_x, x0, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_p, p0_cov, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   TrajectoryParams P;
@@ -729,17 +665,9 @@ int curvis_photon_trajectories(curvis_ctx *ctx, const curvis_metric *metric, uin
   P.iterations = iterations;
   P.delta = delta;
   const unsigned blocks = (n_photons + 63u) / 64u;
-  switch (metric->kind) {
-    case CURVIS_METRIC_ELLIS:
-      hipLaunchKernelGGL((trajectory_kernel<cvk::METRIC_ELLIS>), dim3(blocks), dim3(64), 0, ctx->stream, P);
-      break;
-    case CURVIS_METRIC_INTERSTELLAR:
-      hipLaunchKernelGGL((trajectory_kernel<cvk::METRIC_INTERSTELLAR>), dim3(blocks), dim3(64), 0, ctx->stream, P);
-      break;
-    default:
-      hipLaunchKernelGGL((trajectory_kernel<cvk::METRIC_FLAT>), dim3(blocks), dim3(64), 0, ctx->stream, P);
-      break;
-  }
+  with_kind(metric->kind, [&](auto K) {
+    hipLaunchKernelGGL((trajectory_kernel<decltype(K)::value>), dim3(blocks), dim3(64), 0, ctx->stream, P);
+  });
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -841,12 +769,13 @@ int curvis_host_alloc(size_t bytes, void **out) {
   return CURVIS_OK;
 }
 void curvis_host_free(void *p) {
-  if (p) (void)hipHostFree(p);
+  PinnedBuffer<unsigned char> adopted; /* freed as it leaves the scope */
+  adopted.p = (unsigned char *)p;
 }
 
 int curvis_ctx_framebuffer(curvis_ctx *ctx, void **dev_ptr, size_t *bytes) {
   if (!ctx) return CURVIS_E_INVALID;
-  if (dev_ptr) *dev_ptr = ctx->d_fb;
+  if (dev_ptr) *dev_ptr = ctx->d_fb.p;
   if (bytes) *bytes = ctx->fb_bytes;
   return CURVIS_OK;
 }
@@ -886,162 +815,123 @@ int curvis_ctx_download_wait(curvis_ctx *ctx) {
   return download_wait(ctx);
 }
 
+} /* extern "C" */
+
+namespace {
+
+/* ---- options: ONE table of keys.  curvis_ctx_set_option and curvis_ctx_get_option walk it; a key without a writer is a statistic
+ * (read-only: setting it is refused like a key that does not exist), a key without a reader is a test hook that is consumed by
+ * the code it arms.  Values travel as int64_t and are stored through the type named here. */
+struct OptionEntry {
+  const char *key;
+  int64_t (*read)(const curvis_ctx *);  /* or null */
+  int (*write)(curvis_ctx *, int64_t);  /* or null */
+};
+#define OPT_READ(expr) [](const curvis_ctx *c) -> int64_t { return (int64_t)(expr); }
+#define OPT_WRITE(field, type) [](curvis_ctx *c, int64_t v) -> int { c->field = (type)v; return CURVIS_OK; }
+#define OPT_RW(field, type) {#field, OPT_READ(c->field), OPT_WRITE(field, type)}
+#define OPT_RO(key, expr) {key, OPT_READ(expr), nullptr}
+
+/* "async_download" / "async_streams" (fb_download in render_host.h, deflate_frames_impl in png_host.h): switching one off waits for
+ * what is in flight first, and keeps the flag if that wait fails */
+int drain_before_switching_off(curvis_ctx *c, int64_t v) {
+  if (v) return CURVIS_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return download_wait(c);
+}
+
+const OptionEntry kOptions[] = {
+    OPT_RW(variant, int),
+    OPT_RW(refill_threshold, int),
+    OPT_RW(blocks_per_cu, int),
+    OPT_RW(block_threads, int),
+    OPT_RW(relay_segment, int),
+    OPT_RW(relay_max_hops, int),
+    OPT_RW(relay_max_parks, int),
+    OPT_RW(relay_recheck_every, int),
+    {"async_download", OPT_READ(c->async_download),
+     [](curvis_ctx *c, int64_t v) -> int {
+       if (int rc = drain_before_switching_off(c, v)) return rc;
+       c->async_download = v ? 1 : 0;
+       return CURVIS_OK;
+     }},
+    {"async_streams", OPT_READ(c->async_streams),
+     [](curvis_ctx *c, int64_t v) -> int {
+       if (int rc = drain_before_switching_off(c, v)) return rc;
+       c->async_streams = v ? 1 : 0;
+       return CURVIS_OK;
+     }},
+    OPT_RW(relay_max_frames, int),
+    OPT_RW(relay_min_blocks, long long),
+    OPT_RW(relay_verify, int),
+    {"relay_auto_verify", OPT_READ(c->relay_auto_verify),
+     [](curvis_ctx *c, int64_t v) -> int {
+       c->relay_auto_verify = (int)v;
+       c->relay_verified.clear(); /* switching it (back) on checks every shape afresh */
+       return CURVIS_OK;
+     }},
+    {"relay_test_corrupt", nullptr, OPT_WRITE(relay_test_corrupt, int)}, /* consumed by launch_relay */
+    OPT_RW(relay_disabled, int),
+    {"relay_test_fault", nullptr, OPT_WRITE(relay_test_fault, int)},     /* consumed by render_chunk's re-launch loop */
+    OPT_RW(fast_math, int),
+    OPT_RW(fuse_shade, int),
+    OPT_RW(device_sampler, int),
+    {"device_sampler_min_frames", OPT_READ(c->device_sampler_min_frames),
+     [](curvis_ctx *c, int64_t v) -> int {
+       c->device_sampler_min_frames = v < 1 ? 1 : (int)v;
+       return CURVIS_OK;
+     }},
+    OPT_RW(sampling_speculation, int),
+    OPT_RW(sampling_speculation_first, int),
+    OPT_RW(max_store_bytes, size_t),
+    /* statistics */
+    OPT_RO("relay_mismatches", c->relay_mismatches),
+    OPT_RO("relay_verified_shapes", c->relay_verified.size()),
+    OPT_RO("relay_checks", c->relay_checks),
+    OPT_RO("last_png_stream_bytes", c->last_png_stream_bytes),
+    OPT_RO("streams_pending", c->streams_pending ? 1 : 0),
+    OPT_RO("downloads_overlapped", c->downloads_overlapped),
+    OPT_RO("download_pending", c->dl_pending ? 1 : 0),
+    OPT_RO("relay_fallbacks", c->relay_fallbacks),
+    OPT_RO("last_frames", c->last_frame_stats.size()),
+    OPT_RO("last_relay_launches", c->last_relay_launches),
+    OPT_RO("last_relay_parks", c->last_relay_parks),
+    OPT_RO("last_relay_waiters", c->last_relay_waiters),
+    OPT_RO("last_sampler_path", c->last_sampler_path),
+    OPT_RO("last_sampling_chains", c->last_sampling_chains),
+    OPT_RO("last_sampling_prefetched", c->last_sampling_prefetched),
+    OPT_RO("prefetches", c->prefetches),
+    OPT_RO("prefetch_hits", c->prefetch_hits),
+    OPT_RO("last_sampling_launches", c->last_sampling_launches),
+    OPT_RO("last_sampling_evaluated", c->last_sampling_evaluated),
+};
+#undef OPT_RO
+#undef OPT_RW
+#undef OPT_WRITE
+#undef OPT_READ
+
+const OptionEntry *find_option(const char *key) {
+  for (const OptionEntry &o : kOptions)
+    if (std::strcmp(o.key, key) == 0) return &o;
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
 int curvis_ctx_set_option(curvis_ctx *ctx, const char *key, int64_t value) {
   if (!ctx || !key) return CURVIS_E_INVALID;
-  const std::string k(key);
-  if (k == "variant")
-    ctx->variant = (int)value;
-  else if (k == "refill_threshold")
-    ctx->refill_threshold = (int)value;
-  else if (k == "blocks_per_cu")
-    ctx->blocks_per_cu = (int)value;
-  else if (k == "block_threads")
-    ctx->block_threads = (int)value;
-  else if (k == "relay_segment")
-    ctx->relay_segment = (int)value;
-  else if (k == "relay_max_hops")
-    ctx->relay_max_hops = (int)value;
-  else if (k == "relay_max_parks")
-    ctx->relay_max_parks = (int)value;
-  else if (k == "relay_recheck_every")
-    ctx->relay_recheck_every = (int)value;
-  else if (k == "async_download") { /* overlapped download of the frames, see fb_download (render_host.h) */
-    if (!value) {
-      HIP_TRY(ctx, hipSetDevice(ctx->device));
-      const int rc = download_wait(ctx);
-      if (rc) return rc;
-    }
-    ctx->async_download = value ? 1 : 0;
-  } else if (k == "async_streams") { /* curvis_ctx_deflate_frames returns with its streams still on their way: png_host.h */
-    if (!value) {
-      HIP_TRY(ctx, hipSetDevice(ctx->device));
-      const int rc = download_wait(ctx);
-      if (rc) return rc;
-    }
-    ctx->async_streams = value ? 1 : 0;
-  } else if (k == "relay_max_frames")
-    ctx->relay_max_frames = (int)value;
-  else if (k == "relay_min_blocks")
-    ctx->relay_min_blocks = (long long)value;
-  else if (k == "relay_verify")
-    ctx->relay_verify = (int)value;
-  else if (k == "relay_auto_verify") {
-    ctx->relay_auto_verify = (int)value;
-    ctx->relay_verified.clear(); /* switching it (back) on checks every shape afresh */
-  } else if (k == "relay_test_corrupt")
-    ctx->relay_test_corrupt = (int)value;
-  else if (k == "relay_disabled")
-    ctx->relay_disabled = (int)value;
-  else if (k == "relay_test_fault")
-    ctx->relay_test_fault = (int)value;
-
-  else if (k == "fast_math")
-    ctx->fast_math = (int)value;
-  else if (k == "fuse_shade")
-    ctx->fuse_shade = (int)value;
-  else if (k == "device_sampler")
-    ctx->device_sampler = (int)value;
-  else if (k == "device_sampler_min_frames")
-    ctx->device_sampler_min_frames = value < 1 ? 1 : (int)value;
-  else if (k == "sampling_speculation")
-    ctx->sampling_speculation = (int)value;
-  else if (k == "sampling_speculation_first")
-    ctx->sampling_speculation_first = (int)value;
-  else if (k == "max_store_bytes")
-    ctx->max_store_bytes = (size_t)value;
-  else
-    return fail(ctx, CURVIS_E_INVALID, "unknown option " + k);
-  return CURVIS_OK;
+  const OptionEntry *o = find_option(key);
+  if (!o || !o->write) return fail(ctx, CURVIS_E_INVALID, std::string("unknown option ") + key);
+  return o->write(ctx, value);
 }
 
 int curvis_ctx_get_option(const curvis_ctx *ctx, const char *key, int64_t *value) {
   if (!ctx || !key || !value) return CURVIS_E_INVALID;
-  const std::string k(key);
-  if (k == "variant")
-    *value = ctx->variant;
-  else if (k == "refill_threshold")
-    *value = ctx->refill_threshold;
-  else if (k == "blocks_per_cu")
-    *value = ctx->blocks_per_cu;
-  else if (k == "block_threads")
-    *value = ctx->block_threads;
-  else if (k == "relay_segment")
-    *value = ctx->relay_segment;
-  else if (k == "relay_max_hops")
-    *value = ctx->relay_max_hops;
-  else if (k == "relay_max_parks")
-    *value = ctx->relay_max_parks;
-  else if (k == "relay_max_frames")
-    *value = ctx->relay_max_frames;
-  else if (k == "relay_min_blocks")
-    *value = ctx->relay_min_blocks;
-  else if (k == "relay_verify")
-    *value = ctx->relay_verify;
-  else if (k == "relay_disabled")
-    *value = ctx->relay_disabled;
-  else if (k == "relay_auto_verify")
-    *value = ctx->relay_auto_verify;
-  else if (k == "relay_mismatches")
-    *value = ctx->relay_mismatches;
-  else if (k == "relay_verified_shapes")
-    *value = (int64_t)ctx->relay_verified.size();
-  else if (k == "relay_checks")
-    *value = (int64_t)ctx->relay_checks;
-  else if (k == "last_png_stream_bytes")
-    *value = (int64_t)ctx->last_png_stream_bytes;
-  else if (k == "relay_recheck_every")
-    *value = ctx->relay_recheck_every;
-  else if (k == "async_download")
-    *value = ctx->async_download;
-  else if (k == "async_streams")
-    *value = ctx->async_streams;
-  else if (k == "streams_pending")
-    *value = ctx->streams_pending ? 1 : 0;
-  else if (k == "downloads_overlapped")
-    *value = (int64_t)ctx->downloads_overlapped;
-  else if (k == "download_pending")
-    *value = ctx->dl_pending ? 1 : 0;
-  else if (k == "relay_fallbacks")
-    *value = ctx->relay_fallbacks;
-  else if (k == "last_frames")
-    *value = (int64_t)ctx->last_frame_stats.size();
-  else if (k == "last_relay_launches")
-    *value = ctx->last_relay_launches;
-  else if (k == "last_relay_parks")
-    *value = (int64_t)ctx->last_relay_parks;
-  else if (k == "last_relay_waiters")
-    *value = (int64_t)ctx->last_relay_waiters;
-
-  else if (k == "fast_math")
-    *value = ctx->fast_math;
-  else if (k == "fuse_shade")
-    *value = ctx->fuse_shade;
-  else if (k == "sampling_speculation")
-    *value = ctx->sampling_speculation;
-  else if (k == "sampling_speculation_first")
-    *value = ctx->sampling_speculation_first;
-  else if (k == "device_sampler")
-    *value = ctx->device_sampler;
-  else if (k == "device_sampler_min_frames")
-    *value = ctx->device_sampler_min_frames;
-  else if (k == "last_sampler_path")
-    *value = ctx->last_sampler_path;
-  else if (k == "last_sampling_chains")
-    *value = ctx->last_sampling_chains;
-  else if (k == "last_sampling_prefetched")
-    *value = ctx->last_sampling_prefetched;
-  else if (k == "prefetches")
-    *value = (int64_t)ctx->prefetches;
-  else if (k == "prefetch_hits")
-    *value = (int64_t)ctx->prefetch_hits;
-  else if (k == "last_sampling_launches")
-    *value = ctx->last_sampling_launches;
-  else if (k == "last_sampling_evaluated")
-    *value = (int64_t)ctx->last_sampling_evaluated;
-  else if (k == "max_store_bytes")
-    *value = (int64_t)ctx->max_store_bytes;
-  else
-    return CURVIS_E_INVALID;
+  const OptionEntry *o = find_option(key);
+  if (!o || !o->read) return CURVIS_E_INVALID;
+  *value = o->read(ctx);
   return CURVIS_OK;
 }
 
@@ -1049,22 +939,18 @@ int curvis_selftest_math(curvis_ctx *ctx, int op, const double *a, const double 
   if (!ctx || !a || !out) return CURVIS_E_INVALID;
   if (n == 0) return CURVIS_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  double *da = nullptr, *db = nullptr, *dout = nullptr;
-  HIP_TRY(ctx, hipMalloc((void **)&da, n * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void **)&dout, n * sizeof(double)));
+  DeviceBuffer<double> da, db, dout;
+  if (int rc = da.reserve(ctx, n)) return rc;
+  if (int rc = dout.reserve(ctx, n)) return rc;
   HIP_TRY(ctx, hipMemcpy(da, a, n * sizeof(double), hipMemcpyHostToDevice));
   if (b) {
-    HIP_TRY(ctx, hipMalloc((void **)&db, n * sizeof(double)));
+    if (int rc = db.reserve(ctx, n)) return rc;
     HIP_TRY(ctx, hipMemcpy(db, b, n * sizeof(double), hipMemcpyHostToDevice));
   }
-  hipLaunchKernelGGL(selftest_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, da, db,
-                     dout, n);
+  hipLaunchKernelGGL(selftest_math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, da.p, db.p, dout.p, n);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipMemcpy(out, dout, n * sizeof(double), hipMemcpyDeviceToHost));
-  (void)hipFree(da);
-  (void)hipFree(dout);
-  if (db) (void)hipFree(db);
   return CURVIS_OK;
 }
 
@@ -1073,24 +959,18 @@ int curvis_selftest_math3(curvis_ctx *ctx, int op, const double *a, const double
   if (n == 0) return CURVIS_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const double *in[3] = {a, b, c};
-  double *dev[4] = {nullptr, nullptr, nullptr, nullptr};
-  int rc = CURVIS_OK;
-  for (int k = 0; k < 4 && rc == CURVIS_OK; ++k) {
+  DeviceBuffer<double> dev[4]; /* a, b, c (each may be absent), out */
+  for (int k = 0; k < 4; ++k) {
     if (k < 3 && !in[k]) continue;
-    if (hipMalloc((void **)&dev[k], n * sizeof(double)) != hipSuccess ||
-        (k < 3 && hipMemcpy(dev[k], in[k], n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess))
-      rc = fail(ctx, CURVIS_E_HIP, "curvis_selftest_math3: device buffer");
+    if (int rc = dev[k].reserve(ctx, n)) return rc;
+    if (k < 3) HIP_TRY(ctx, hipMemcpy(dev[k], in[k], n * sizeof(double), hipMemcpyHostToDevice));
   }
-  if (rc == CURVIS_OK) {
-    hipLaunchKernelGGL(selftest_math3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, dev[0], dev[1],
-                       dev[2], dev[3], n);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(out, dev[3], n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(ctx, CURVIS_E_HIP, "curvis_selftest_math3: launch");
-  }
-  for (double *d : dev)
-    if (d) (void)hipFree(d);
-  return rc;
+  hipLaunchKernelGGL(selftest_math3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, dev[0].p, dev[1].p, dev[2].p,
+                     dev[3].p, n);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, dev[3], n * sizeof(double), hipMemcpyDeviceToHost));
+  return CURVIS_OK;
 }
 
 int curvis_selftest_fast_step(curvis_ctx *ctx, const curvis_metric *metric, double delta, double max_radius, const double *states,
@@ -1100,32 +980,18 @@ int curvis_selftest_fast_step(curvis_ctx *ctx, const curvis_metric *metric, doub
   if (n == 0) return CURVIS_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const cvk::MetricParams MP = make_metric(*metric);
-  double *din = nullptr, *dout = nullptr;
-  int rc = CURVIS_OK;
-  if (hipMalloc((void **)&din, n * 5 * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&dout, n * CURVIS_FAST_STEP_RECORD * sizeof(double)) != hipSuccess ||
-      hipMemcpy(din, states, n * 5 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-    rc = fail(ctx, CURVIS_E_HIP, "curvis_selftest_fast_step: device buffer");
-  if (rc == CURVIS_OK) {
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    switch (metric->kind) {
-      case CURVIS_METRIC_ELLIS:
-        hipLaunchKernelGGL((selftest_fast_step_kernel<cvk::METRIC_ELLIS>), grid, block, 0, ctx->stream, MP, delta, max_radius, din, n, dout);
-        break;
-      case CURVIS_METRIC_INTERSTELLAR:
-        hipLaunchKernelGGL((selftest_fast_step_kernel<cvk::METRIC_INTERSTELLAR>), grid, block, 0, ctx->stream, MP, delta, max_radius, din, n, dout);
-        break;
-      default:
-        hipLaunchKernelGGL((selftest_fast_step_kernel<cvk::METRIC_FLAT>), grid, block, 0, ctx->stream, MP, delta, max_radius, din, n, dout);
-        break;
-    }
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(out, dout, n * CURVIS_FAST_STEP_RECORD * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
-      rc = fail(ctx, CURVIS_E_HIP, "curvis_selftest_fast_step: launch");
-  }
-  if (din) (void)hipFree(din);
-  if (dout) (void)hipFree(dout);
-  return rc;
+  DeviceBuffer<double> din, dout;
+  if (int rc = din.reserve(ctx, n * 5)) return rc;
+  if (int rc = dout.reserve(ctx, n * CURVIS_FAST_STEP_RECORD)) return rc;
+  HIP_TRY(ctx, hipMemcpy(din, states, n * 5 * sizeof(double), hipMemcpyHostToDevice));
+  with_kind(metric->kind, [&](auto K) {
+    hipLaunchKernelGGL((selftest_fast_step_kernel<decltype(K)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, MP,
+                       delta, max_radius, din.p, n, dout.p);
+  });
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, dout, n * CURVIS_FAST_STEP_RECORD * sizeof(double), hipMemcpyDeviceToHost));
+  return CURVIS_OK;
 }
 
 } /* extern "C" */

@@ -111,9 +111,9 @@ int deflate_frames_impl(curvis_ctx *ctx, uint32_t W, uint32_t H, uint32_t n_fram
   P.staged = (P.row_bytes % kPngChunk) == 0u ? 1 : 0;
   P.grid_x = 8u * ((P.blocks_per_frame + 7u) / 8u);
   const PngScratch L = png_scratch_layout(P);
-  int rc = ensure_device(ctx, ctx->d_png, ctx->png_cap, L.total);
+  int rc = ctx->d_png.reserve(ctx, L.total);
   if (rc) return rc;
-  unsigned char *base = ctx->d_png;
+  unsigned char *base = ctx->d_png.p;
   P.hist = (unsigned *)(base + L.hist);
   P.adler = (unsigned long long *)(base + L.adler);
   P.codes = (unsigned *)(base + L.codes);
@@ -185,14 +185,19 @@ int deflate_frames_impl(curvis_ctx *ctx, uint32_t W, uint32_t H, uint32_t n_fram
     if (rcs) return rcs;
     out_stream = ctx->copy_stream;
   }
-  for (uint32_t f = 0; f < n_frames; ++f)
-    HIP_TRY(ctx, hipMemcpyAsync(out + offsets[f], (const uint8_t *)(P.out + (size_t)f * L.out_words), offsets[f + 1] - offsets[f] - 4,
-                                hipMemcpyDeviceToHost, out_stream));
-  if (async_out) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_streams, ctx->copy_stream));
-    ctx->streams_pending = true;
-  } else {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  /* from the first copy on, transfers into the caller's buffer are in flight: a failure of any call below waits for them
+   * before it is reported (the pattern of fb_download) -- no error return with `out` still being written */
+  ctx->streams_pending = async_out;
+  hipError_t e = hipSuccess;
+  for (uint32_t f = 0; f < n_frames && e == hipSuccess; ++f)
+    e = hipMemcpyAsync(out + offsets[f], (const uint8_t *)(P.out + (size_t)f * L.out_words), offsets[f + 1] - offsets[f] - 4,
+                       hipMemcpyDeviceToHost, out_stream);
+  if (e == hipSuccess && async_out) e = hipEventRecord(ctx->ev_streams, ctx->copy_stream);
+  if (e != hipSuccess || !async_out) {
+    const hipError_t es = hipStreamSynchronize(out_stream);
+    ctx->streams_pending = false;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(ctx, CURVIS_E_HIP, std::string("streams to the host: ") + hipGetErrorString(e));
   }
   const auto t_4 = tnow();
   const unsigned long long n = (unsigned long long)H * ((unsigned long long)W * 3 + 1);

@@ -1,5 +1,6 @@
-/* render_host.h -- host side of the per-pixel path: struct curvis_ctx, launch selection (static / relay / persistent),
- * render_impl with per-frame statistics and the relay seat belt.
+/* render_host.h -- host side of the per-pixel path: struct curvis_ctx, the metric / step-flavour dispatcher, launch selection
+ * (static / relay / persistent), render_impl and its pieces (path decision, one chunk of frames, the relay seat belt), per-frame
+ * statistics.
  * Part of the ONE translation unit curvis_hip.hip (included there, nowhere else). */
 #pragma once
 
@@ -11,27 +12,26 @@ thread_local std::string g_create_error;
 
 }  // namespace
 
+/* Every HIP resource below is held by an owning type of hip_owned.h, so `delete ctx` releases them all (curvis_ctx_destroy
+ * synchronises the streams first: that, not the order of the members, is what makes the order of destruction immaterial). */
 struct curvis_ctx {
   int device = -1;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Stream stream;
+  Event ev0, ev1;
   hipDeviceProp_t prop{};
   std::string err;
   /* skies */
-  void *d_sky[2] = {nullptr, nullptr};
-  bool sky_owned[2] = {false, false};
-  unsigned sky_w[2] = {0, 0}, sky_h[2] = {0, 0};
+  SkyTexture sky[2];
   double sky_inv_rot[2][9];
   /* frame resources */
-  unsigned char *d_fb = nullptr;
-  size_t fb_cap = 0, fb_bytes = 0;
+  DeviceBuffer<unsigned char> d_fb;
+  size_t fb_bytes = 0;
   /* overlapped download (option "async_download", fb_begin_write / fb_download below): a copy stream of its own, the second
    * frame buffer the next render call writes while the copy engine still reads the first, and the one download in flight */
   int async_download = 0;
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_fb = nullptr, ev_dl = nullptr; /* frames complete on `stream` / download complete on `copy_stream` */
-  unsigned char *d_fb_alt = nullptr;
-  size_t fb_alt_cap = 0;
+  Stream copy_stream;
+  Event ev_fb, ev_dl; /* frames complete on `stream` / download complete on `copy_stream` */
+  DeviceBuffer<unsigned char> d_fb_alt;
   bool dl_pending = false;
   const unsigned char *dl_src = nullptr;       /* the device buffer the pending download reads */
   uint64_t downloads_overlapped = 0;           /* downloads queued behind the caller's back so far (option, read-only) */
@@ -39,15 +39,12 @@ struct curvis_ctx {
    * stream); they are there after curvis_ctx_download_wait, and before the next deflate call touches the scratch they are read from */
   int async_streams = 0;
   bool streams_pending = false;
-  hipEvent_t ev_streams = nullptr;
-  curvis_ray_debug *d_dbg = nullptr;
-  size_t dbg_cap = 0;
-  unsigned char *d_store = nullptr; /* RayStore arrays, carved from one allocation */
-  unsigned char *d_rq = nullptr;    /* RelayQueue + ticket ring of the relay kernel */
-  unsigned char *d_verify = nullptr; /* copy of the relay kernel's frame while the static kernel re-renders it (seat belt) */
-  size_t verify_cap = 0;
-  unsigned char *d_png = nullptr;    /* scratch of the device PNG front end (kernels_png.h): histograms, codes, offsets, streams */
-  size_t png_cap = 0;
+  Event ev_streams;
+  DeviceBuffer<curvis_ray_debug> d_dbg;
+  DeviceBuffer<unsigned char> d_store;  /* RayStore arrays, carved from one allocation */
+  DeviceBuffer<unsigned char> d_rq;     /* RelayQueue + ticket ring of the relay kernel */
+  DeviceBuffer<unsigned char> d_verify; /* copy of the relay kernel's frame while the static kernel re-renders it (seat belt) */
+  DeviceBuffer<unsigned char> d_png;    /* scratch of the device PNG front end (kernels_png.h): histograms, codes, offsets, streams */
   double last_png_ms = 0.0;          /* HIP-event time of the last curvis_ctx_deflate_frames */
   size_t last_png_stream_bytes = 0;  /* bytes the streams of the last curvis_ctx_deflate_frames take (also when it failed for want of room) */
   int relay_segment = 0;            /* steps between two hand-over points; 0 = automatic */
@@ -81,24 +78,17 @@ struct curvis_ctx {
   unsigned relay_resident_blocks[3][2] = {{0, 0}, {0, 0}, {0, 0}}; /* cached occupancy query per kernel instantiation */
   int relay_resident_threads = 0;                                  /* ... valid for this workgroup size */
   int block_threads = 0; /* workgroup size of the static / relay kernels: 64, 128 or 256; 0 = automatic */
-  size_t store_cap = 0;
-  hipEvent_t ev2 = nullptr;
+  Event ev2;
   /* efficient mode scratch (device) */
-  unsigned char *d_eff = nullptr;
-  size_t eff_cap = 0;
-  unsigned char *h_eff = nullptr; /* pinned staging mirror of d_eff for the sampling launches */
-  size_t h_eff_cap = 0;
+  DeviceBuffer<unsigned char> d_eff;
+  PinnedBuffer<unsigned char> h_eff; /* staging mirror of d_eff for the sampling launches */
   /* sample tables of the last efficient render, per frame (for tests / statistics) */
   std::vector<std::vector<cvs::BiPoint>> last_samples;
   std::vector<curvis_sampling_info> last_sampling_info;
-  cvk::CameraParams *d_cams = nullptr;
-  size_t cams_cap = 0;
-  cvk::CameraParams *h_cams = nullptr; /* pinned */
-  size_t h_cams_cap = 0;
-  unsigned long long *d_counters = nullptr; /* FrameCounters block, sized for the largest launch so far */
-  size_t counters_cap = 0;
-  unsigned long long *h_counters = nullptr; /* pinned mirror (+ 8 words for the relay queue header) */
-  size_t h_counters_cap = 0;
+  DeviceBuffer<cvk::CameraParams> d_cams;
+  PinnedBuffer<cvk::CameraParams> h_cams;
+  DeviceBuffer<unsigned long long> d_counters; /* FrameCounters block, sized for the largest launch so far */
+  PinnedBuffer<unsigned long long> h_counters; /* mirror (+ 8 words for the relay queue header) */
   /* statistics of the last render, per frame (curvis_ctx_frame_stats) */
   std::vector<curvis_stats> last_frame_stats;
   /* options */
@@ -121,24 +111,28 @@ struct curvis_ctx {
   /* device-resident sampler: two slots (device buffer + page-locked mirror each) that take turns -- a call samples into one on its own
    * stream, or finds one filled ahead of time by curvis_ctx_prefetch_efficient on `sampler_stream`; the tables of the last render
    * stay readable in their slot (curvis_ctx_samples) until that slot is submitted to again, i.e. for one more submission */
-  struct SamplerSlot {
-    bool valid = false, prefetched = false;
-    unsigned char *d = nullptr, *h = nullptr;
-    size_t d_cap = 0, h_cap = 0, res_bytes = 0, h_res_off = 0;
-    size_t o_tab_off = 0, o_tab_n = 0, o_grid_off = 0, o_grid = 0, o_res = 0, o_tab[7] = {0, 0, 0, 0, 0, 0, 0};
-    hipEvent_t done = nullptr, t0 = nullptr, t1 = nullptr;
-    std::vector<unsigned> job_of_frame;
-    std::vector<double> l_job, l_frame;
-    /* what the tables depend on */
+  struct SamplerKey { /* what the tables of a sampler launch depend on (efficient_host.h sampler_key_equal) */
     curvis_metric metric{};
     uint32_t n_frames = 0, max_iter = 0, alpha_nums = 0, max_iterations_sampling = 0;
-    double params[4] = {0, 0, 0, 0};
+    double max_radius = 0, delta = 0, thr1 = 0, thr2 = 0;
     int fast = 0, speculate = 0;
+    std::vector<double> l_frame; /* radial coordinate of every frame's camera */
+  };
+  struct SamplerSlot {
+    bool valid = false, prefetched = false;
+    DeviceBuffer<unsigned char> d;
+    PinnedBuffer<unsigned char> h;
+    size_t res_bytes = 0, h_res_off = 0;
+    size_t o_tab_off = 0, o_tab_n = 0, o_grid_off = 0, o_grid = 0, o_res = 0, o_tab[7] = {0, 0, 0, 0, 0, 0, 0};
+    Event done, t0, t1;
+    std::vector<unsigned> job_of_frame;
+    std::vector<double> l_job;
+    SamplerKey key;
     uint64_t seq = 0; /* order of submission */
   } samp[2];
   unsigned samp_next = 0;
   uint64_t samp_seq = 0;
-  hipStream_t sampler_stream = nullptr;
+  Stream sampler_stream;
   uint64_t prefetches = 0, prefetch_hits = 0;
   int last_sampling_prefetched = 0;
   struct DevSamples {                /* which slot holds the tables of the last device-sampled call (curvis_ctx_samples fetches on demand) */
@@ -168,22 +162,21 @@ int fail(curvis_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
-#define HIP_TRY(ctx, call)                                                                         \
-  do {                                                                                             \
-    hipError_t e_ = (call);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      return fail(ctx, CURVIS_E_HIP, std::string(#call) + ": " + hipGetErrorString(e_));           \
-  } while (0)
-
-template <typename T>
-int ensure_device(curvis_ctx *ctx, T *&ptr, size_t &cap, size_t need) {
-  if (need <= cap) return CURVIS_OK;
-  if (ptr) HIP_TRY(ctx, hipFree(ptr));
-  ptr = nullptr;
-  cap = 0;
-  HIP_TRY(ctx, hipMalloc((void **)&ptr, need * sizeof(T)));
-  cap = need;
-  return CURVIS_OK;
+/* ---- the metric kind and the step flavour, from run-time values to template arguments -----------------------------------
+ * with_kind(kind, [&](auto K) { ... decltype(K)::value ... }) calls the lambda with the kind as a type; an unknown kind is FLAT
+ * (curvis_metric_validate is what refuses it).  with_flag does the same for a bool.  The lambda's result is the call's result:
+ * HIP_TRY inside it returns from the LAMBDA, so a caller hands that int on. */
+template <typename F>
+auto with_kind(int kind, F &&f) {
+  switch (kind) {
+    case CURVIS_METRIC_ELLIS: return f(std::integral_constant<int, cvk::METRIC_ELLIS>{});
+    case CURVIS_METRIC_INTERSTELLAR: return f(std::integral_constant<int, cvk::METRIC_INTERSTELLAR>{});
+    default: return f(std::integral_constant<int, cvk::METRIC_FLAT>{});
+  }
+}
+template <typename F>
+auto with_flag(bool flag, F &&f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
 }
 
 /* ---- overlapped download of the frames (option "async_download" = 1) -------------------------------------------------
@@ -207,21 +200,16 @@ int download_wait(curvis_ctx *ctx) {
   return CURVIS_OK;
 }
 int ensure_copy_stream(curvis_ctx *ctx) {
-  if (!ctx->copy_stream) {
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fb, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_dl, hipEventDisableTiming));
-  }
-  if (!ctx->ev_streams) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_streams, hipEventDisableTiming));
-  return CURVIS_OK;
+  if (int rc = ctx->copy_stream.ensure(ctx, hipStreamNonBlocking)) return rc;
+  if (int rc = ctx->ev_fb.ensure(ctx, hipEventDisableTiming)) return rc;
+  if (int rc = ctx->ev_dl.ensure(ctx, hipEventDisableTiming)) return rc;
+  return ctx->ev_streams.ensure(ctx, hipEventDisableTiming);
 }
 /* call before anything writes `bytes` of frames into ctx->d_fb */
 int fb_begin_write(curvis_ctx *ctx, size_t bytes) {
-  if (ctx->dl_pending && ctx->dl_src == ctx->d_fb) { /* the copy engine is still reading it: write the other one */
+  if (ctx->dl_pending && ctx->dl_src == ctx->d_fb.p) /* the copy engine is still reading it: write the other one */
     std::swap(ctx->d_fb, ctx->d_fb_alt);
-    std::swap(ctx->fb_cap, ctx->fb_alt_cap);
-  }
-  return ensure_device(ctx, ctx->d_fb, ctx->fb_cap, bytes);
+  return ctx->d_fb.reserve(ctx, bytes);
 }
 /* frames [0, bytes) of ctx->d_fb -> rgb_out, after everything queued on ctx->stream so far.  Synchronous unless the
  * option is set; either way ctx->stream is idle on return. */
@@ -260,15 +248,8 @@ int fb_download(curvis_ctx *ctx, unsigned char *rgb_out, size_t bytes) {
 int prepare_counters(curvis_ctx *ctx, unsigned n_frames, FrameCounters &C, unsigned slots = 0u) {
   C.slots = slots ? slots : counter_slots_for(n_frames); /* a power of two */
   const size_t words = counter_words(n_frames, C.slots);
-  int rc = ensure_device(ctx, ctx->d_counters, ctx->counters_cap, words);
-  if (rc) return rc;
-  if (ctx->h_counters_cap < words + 8) {
-    if (ctx->h_counters) HIP_TRY(ctx, hipHostFree(ctx->h_counters));
-    ctx->h_counters = nullptr;
-    ctx->h_counters_cap = 0;
-    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_counters, sizeof(unsigned long long) * (words + 8)));
-    ctx->h_counters_cap = words + 8;
-  }
+  if (int rc = ctx->d_counters.reserve(ctx, words)) return rc;
+  if (int rc = ctx->h_counters.reserve(ctx, words + 8)) return rc;
   C.base = ctx->d_counters;
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * words, ctx->stream));
   return CURVIS_OK;
@@ -280,6 +261,15 @@ void sum_frame_counters(const unsigned long long *h, unsigned slots, unsigned f,
     const unsigned long long *line = h + (size_t)CNT_STRIDE * (1u + (size_t)f * slots + r);
     for (int k = 0; k < FC_N; ++k) out[k] += line[k];
   }
+}
+/* the count fields of a statistics record from one summed counter line */
+void counts_to_stats(const uint64_t fc[FC_N], curvis_stats &s) {
+  s.rays = fc[FC_RAYS];
+  s.steps = fc[FC_STEPS];
+  s.n_pos = fc[FC_POS];
+  s.n_neg = fc[FC_NEG];
+  s.n_none = fc[FC_NONE];
+  s.n_oob = fc[FC_OOB];
 }
 
 cvk::MetricParams make_metric(const curvis_metric &m) {
@@ -331,6 +321,15 @@ cvk::CameraParams make_camera(const curvis_camera &c) {
   return C;
 }
 
+cvk::SkyParams make_sky_params(const curvis_ctx *ctx, int k) {
+  cvk::SkyParams S;
+  S.texels = (const unsigned *)ctx->sky[k].texels;
+  S.w = ctx->sky[k].w;
+  S.h = ctx->sky[k].h;
+  for (int i = 0; i < 9; ++i) S.inv_rot[i] = ctx->sky_inv_rot[k][i];
+  return S;
+}
+
 /* workgroup size of the static and relay kernels ("block_threads"; total_rays is a multiple of 64) */
 unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
   (void)kind;
@@ -342,9 +341,9 @@ unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
 template <int KIND, bool FAST>
 int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
   const size_t bytes = sizeof(RelayQueue) + sizeof(unsigned) * kRelayRing;
-  if (!ctx->d_rq) HIP_TRY(ctx, hipMalloc((void **)&ctx->d_rq, bytes));
+  if (int rc = ctx->d_rq.reserve(ctx, bytes)) return rc;
   RelayArgs A;
-  A.q = (RelayQueue *)ctx->d_rq;
+  A.q = (RelayQueue *)ctx->d_rq.p;
   A.n_tiles = P.total_rays / 64ull;
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const unsigned long long fresh_blocks = relay_only ? 0ull : (P.total_rays + bt - 1ull) / bt;
@@ -413,27 +412,23 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int 
   return CURVIS_OK;
 }
 
-template <int KIND>
-int launch_integrate_kind(curvis_ctx *ctx, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P) {
-  if (phi)
-    return fast ? launch_integrate<KIND, true, true>(ctx, P, false, 0) : launch_integrate<KIND, true, false>(ctx, P, false, 0);
-  return fast ? launch_integrate<KIND, false, true>(ctx, P, fused, relay) : launch_integrate<KIND, false, false>(ctx, P, fused, relay);
-}
+
+/* phi is integrated for the debug dump only, which is never fused and never relayed */
 int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P) {
-  switch (kind) {
-    case CURVIS_METRIC_ELLIS: return launch_integrate_kind<cvk::METRIC_ELLIS>(ctx, phi, fast, fused, relay, P);
-    case CURVIS_METRIC_INTERSTELLAR: return launch_integrate_kind<cvk::METRIC_INTERSTELLAR>(ctx, phi, fast, fused, relay, P);
-    default: return launch_integrate_kind<cvk::METRIC_FLAT>(ctx, phi, fast, fused, relay, P);
-  }
+  return with_kind(kind, [&](auto K) {
+    constexpr int KIND = decltype(K)::value;
+    if (phi) return with_flag(fast, [&](auto F) { return launch_integrate<KIND, true, decltype(F)::value>(ctx, P, false, 0); });
+    return with_flag(fast, [&](auto F) { return launch_integrate<KIND, false, decltype(F)::value>(ctx, P, fused, relay); });
+  });
 }
 
-template <int KIND>
-int launch_shade_kind(curvis_ctx *ctx, bool debug, const ShadeParams &P) {
+int launch_shade(curvis_ctx *ctx, int kind, bool debug, const ShadeParams &P) {
   const unsigned long long blocks = (P.n_pixels + 255ull) / 256ull;
-  if (debug)
-    hipLaunchKernelGGL((shade_kernel<KIND, true>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
-  else
-    hipLaunchKernelGGL((shade_kernel<KIND, false>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
+  with_kind(kind, [&](auto K) {
+    with_flag(debug, [&](auto D) {
+      hipLaunchKernelGGL((shade_kernel<decltype(K)::value, decltype(D)::value>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
+    });
+  });
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
@@ -453,6 +448,307 @@ RayStore carve_store(unsigned char *base, size_t npix) {
 }
 constexpr size_t kStoreBytesPerPixel = 6 * sizeof(double) + sizeof(unsigned) + sizeof(int);
 
+/* ---- render_impl and its pieces ------------------------------------------------------------------------------------------ */
+
+/* one call: its arguments, and the sizes the argument checks derive from them */
+struct BruteCall {
+  const curvis_metric *metric;
+  const curvis_camera *cams;
+  uint32_t n_frames, max_iter;
+  double max_radius, delta;
+  uint8_t *rgb_out;
+  curvis_ray_debug *dbg_out;
+  curvis_stats *stats;
+  uint32_t row_begin, row_count; /* row band (curvis_render_brute_rows); row_count = 0: the whole frame */
+  uint32_t W = 0, H = 0;         /* H: the rows this call renders */
+  size_t npix = 0, fb_bytes = 0;
+};
+int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
+                double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin,
+                uint32_t row_count);
+/* the same frames once more (the relay kernel's fall-backs and its checker): with the caller's outputs, or into d_fb only */
+int render_again(curvis_ctx *ctx, const BruteCall &c, bool deliver) {
+  return render_impl(ctx, c.metric, c.cams, c.n_frames, c.max_iter, c.max_radius, c.delta, deliver ? c.rgb_out : nullptr,
+                     deliver ? c.dbg_out : nullptr, deliver ? c.stats : nullptr, c.row_begin, c.row_count);
+}
+/* a piece's answer when the relay kernel has just been switched off for this context (waves that gave up, a checked launch that
+ * differs): render_impl renders the call again -- the static kernel takes it */
+constexpr int kRenderAgain = 1;
+
+/* which kernels render the call, and how many frames at a time */
+struct RenderPath {
+  bool fused, relay;
+  uint32_t chunk;     /* frames per launch */
+  size_t store_bytes; /* of the ray store: the relay kernel's staging area, or the unfused path's final states; 0 = none */
+};
+RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
+  RenderPath p;
+  /* fused shading: static kernel, no debug dump (option "fuse_shade", default on) -- no ray store at all.
+   * Otherwise frames are rendered in chunks whose ray store stays below max_store_bytes. */
+  p.fused = ctx->variant != 0 && ctx->fuse_shade != 0 && c.dbg_out == nullptr;
+  /* relay kernel ("variant" = 2, and the automatic choice for big enough single images): end-game hand-over of
+   * tiles; only launches of a few frames have a tail worth its staging area (56 B per ray) -- larger batches
+   * use the static kernel, and so do frames too small to have a dispatch phase (measured against the static
+   * kernel: 640x360 +2 %, 720x405 -9 %, 800x450 -9 %, 960x540 -15 %, 1280x720 -6 %, 1920x1080 -3..-5 %,
+   * 2560x1440 -1 %; tools/gpu_relay_sizes.py, tools/gpu_relay_threshold.py) */
+  const unsigned long long tiles = (unsigned long long)((c.W + 7) / 8) * ((c.H + 7) / 8) * c.n_frames;
+  const unsigned long long relay_fresh_blocks = (tiles + 3ull) / 4ull;
+  const unsigned long long relay_min = ctx->relay_min_blocks >= 0 ? (unsigned long long)ctx->relay_min_blocks
+                                                                   : 4ull * (unsigned long long)ctx->prop.multiProcessorCount;
+  const size_t relay_staging = (size_t)tiles * 64u * kStoreBytesPerPixel;
+  p.relay = (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
+            relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
+  p.chunk = c.n_frames;
+  p.store_bytes = p.relay ? relay_staging : 0;
+  if (!p.fused) {
+    p.chunk = (uint32_t)std::max<size_t>(1, ctx->max_store_bytes / (c.npix * kStoreBytesPerPixel));
+    if (p.chunk > c.n_frames) p.chunk = c.n_frames;
+    p.store_bytes = (size_t)p.chunk * c.npix * kStoreBytesPerPixel;
+  }
+  return p;
+}
+
+struct RenderTotals { /* over the chunks of a call */
+  uint64_t counts[FC_N] = {0};
+  double integrate_ms = 0.0, shade_ms = 0.0;
+};
+
+/* frames [f0, f0 + nf) of the call: parameters, the launch(es), the relay kernel's re-launch loop, counters -> statistics */
+int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, const cvk::MetricParams &MP, uint32_t f0, uint32_t nf,
+                 RenderTotals &tot) {
+  const bool relay = path.relay, fused = path.fused;
+  const bool phi = c.dbg_out != nullptr; /* phi is only read by the debug dump on this path */
+  const bool fast = ctx->fast_math != 0;
+  FrameCounters FC;
+  int rc = prepare_counters(ctx, nf, FC);
+  if (rc) return rc;
+  const size_t cnt_words = counter_words(nf, FC.slots);
+  IntegrateParams P;
+  P.metric = MP;
+  P.cams = ctx->d_cams + f0;
+  P.n_frames = nf;
+  P.W = c.W;
+  P.H = c.H;
+  P.row0 = c.row_count ? c.row_begin : 0u;
+  P.tiles_x = (c.W + 7) / 8;
+  P.tiles_y = (c.H + 7) / 8;
+  const unsigned long long rpf = (unsigned long long)P.tiles_x * P.tiles_y * 64ull;
+  if (rpf > 0xFFFFFFFFull || rpf * nf / 64ull > 0xFFFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
+  P.rays_per_frame = (unsigned)rpf;
+  P.total_rays = rpf * nf;
+  P.max_iter = c.max_iter;
+  P.max_radius = c.max_radius;
+  P.delta = c.delta;
+  P.store = relay ? carve_store(ctx->d_store, (size_t)P.total_rays) : fused ? RayStore{} : carve_store(ctx->d_store, (size_t)nf * c.npix);
+  P.counters = FC;
+  for (int k = 0; k < 2; ++k) P.sky[k] = make_sky_params(ctx, k);
+  P.fb = ctx->d_fb + (size_t)f0 * c.npix * 3;
+  P.refill_threshold = ctx->refill_threshold < 1 ? 1 : (ctx->refill_threshold > 64 ? 64 : ctx->refill_threshold);
+  P.fast_ok = cvk::metric_fast_ok(c.metric->kind, MP, c.max_radius) ? 1 : 0;
+  /* diagnostics only (CURVIS_TRACE_FILE): per-wave records of this launch, binary u64 x 4 per wave */
+  DeviceBuffer<unsigned long long> trace;
+  const char *trace_file = getenv("CURVIS_TRACE_FILE");
+  size_t trace_words = (size_t)(P.total_rays / 64ull) * 4u;
+  if (relay) trace_words = (size_t)(P.total_rays / 64ull) * 3u * 4u + 65536u * 16u; /* every wave of the grid */
+  if (trace_file && *trace_file && (ctx->variant != 0 || relay)) {
+    if ((rc = trace.reserve(ctx, trace_words))) return rc;
+    HIP_TRY(ctx, hipMemsetAsync(trace, 0, trace_words * sizeof(unsigned long long), ctx->stream));
+  }
+  P.trace = trace;
+
+  ShadeParams Q;
+  Q.metric = MP;
+  for (int k = 0; k < 2; ++k) Q.sky[k] = P.sky[k];
+  Q.store = P.store;
+  Q.n_pixels = (unsigned long long)nf * c.npix;
+  Q.fb = P.fb;
+  Q.dbg = c.dbg_out ? ctx->d_dbg + (size_t)f0 * c.npix : nullptr;
+  Q.npix = c.npix;
+  Q.counters = FC;
+
+  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  if (trace) {
+    std::vector<unsigned long long> tr(trace_words);
+    HIP_TRY(ctx, hipMemcpyAsync(tr.data(), trace, trace_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (FILE *fp = fopen(trace_file, "wb")) {
+      fwrite(tr.data(), sizeof(unsigned long long), tr.size(), fp);
+      fclose(fp);
+    }
+  }
+  if (!fused) {
+    rc = launch_shade(ctx, c.metric->kind, c.dbg_out != nullptr, Q);
+    if (rc) return rc;
+  }
+  HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+  ctx->last_relay_launches = relay ? 1 : 0;
+  for (;;) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    if (relay) /* queue header rides along with the counters: finished / error */
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters + cnt_words, ctx->d_rq, sizeof(unsigned long long) * 8, hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!relay) break;
+    /* normally the one launch finished every tile; more relay workgroups only if the grid ran out of them
+     * with tiles still parked */
+    const RelayQueue *hq = (const RelayQueue *)(ctx->h_counters + cnt_words);
+    const unsigned long long n_tiles = P.total_rays / 64ull;
+    if (hq->error != 0 || ctx->relay_test_fault) {
+      /* waves gave up waiting for a tile (a logic error, or a dispatcher that did not start the workgroups in
+       * order): not a hang and not a wrong frame -- the frame is rendered again by the static kernel, which has no
+       * inter-workgroup dependency, and this context stops using the relay kernel */
+      ctx->relay_test_fault = 0;
+      ctx->relay_disabled = 1;
+      ctx->relay_fallbacks++;
+      fprintf(stderr, "[curvis] relay kernel: %llu waves gave up waiting (%llu tiles unfinished); falling back to the static kernel for this context\n",
+              (unsigned long long)hq->error, (unsigned long long)(n_tiles - hq->finished));
+      return kRenderAgain;
+    }
+    ctx->last_relay_parks = hq->tail;
+    ctx->last_relay_waiters = hq->head;
+    if (hq->finished >= n_tiles) break;
+    if (ctx->last_relay_launches++ > 64)
+      return fail(ctx, CURVIS_E_HIP, "relay kernel: tiles still unfinished after 64 relay launches");
+    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+  }
+  float ms_i = 0.f, ms_s = 0.f;
+  HIP_TRY(ctx, hipEventElapsedTime(&ms_i, ctx->ev0, ctx->ev1));
+  tot.integrate_ms += ms_i;
+  HIP_TRY(ctx, hipEventElapsedTime(&ms_s, ctx->ev1, ctx->ev2));
+  tot.shade_ms += ms_s;
+  uint64_t launch_steps = 0;
+  for (uint32_t f = 0; f < nf; ++f) {
+    uint64_t fc[FC_N];
+    sum_frame_counters(ctx->h_counters, FC.slots, f, fc);
+    for (int k = 0; k < FC_N; ++k) tot.counts[k] += fc[k];
+    counts_to_stats(fc, ctx->last_frame_stats[f0 + f]);
+    launch_steps += fc[FC_STEPS];
+  }
+  /* the frames of a launch run interleaved on the GPU: times are the launch's, shared out by executed Euler steps */
+  for (uint32_t f = 0; f < nf; ++f) {
+    curvis_stats &fs = ctx->last_frame_stats[f0 + f];
+    const double share = launch_steps ? (double)fs.steps / (double)launch_steps : 1.0 / nf;
+    fs.integrate_ms = ms_i * share;
+    fs.shade_ms = ms_s * share;
+    fs.kernel_ms = fs.integrate_ms + fs.shade_ms;
+    fs.total_ms = fs.kernel_ms;
+  }
+  return CURVIS_OK;
+}
+
+/* what a render leaves in the context for the statistics calls and options: the seat belt's re-render overwrites it, and the relay
+ * launch's values are put back */
+struct LastRenderStats {
+  std::vector<curvis_stats> frames;
+  uint32_t relay_launches;
+  uint64_t relay_parks, relay_waiters;
+  double integrate_ms, shade_ms;
+  explicit LastRenderStats(const curvis_ctx *c)
+      : frames(c->last_frame_stats), relay_launches(c->last_relay_launches), relay_parks(c->last_relay_parks),
+        relay_waiters(c->last_relay_waiters), integrate_ms(c->last_integrate_ms), shade_ms(c->last_shade_ms) {}
+  void restore(curvis_ctx *c) const {
+    c->last_frame_stats = frames;
+    c->last_relay_launches = relay_launches;
+    c->last_relay_parks = relay_parks;
+    c->last_relay_waiters = relay_waiters;
+    c->last_integrate_ms = integrate_ms;
+    c->last_shade_ms = shade_ms;
+  }
+};
+
+/* The relay kernel's hand-over rests on gfx950 facts (write-through sc0 sc1 stores, s_waitcnt vmcnt(0) before
+ * the ticket store) rather than on the HIP memory model, so it wears a seat belt: the first relay launch of every
+ * launch shape is repeated by the static kernel -- no inter-workgroup traffic at all -- and frames and counters are
+ * compared.  Option "relay_verify" = 1 checks EVERY launch and makes a difference an error (debugging); the automatic
+ * check (option "relay_auto_verify", default 1) costs one static launch per shape and context and, on a difference,
+ * reports it on stderr, counts it ("relay_mismatches"), switches the context to the static kernel and asks for the call to be
+ * rendered again (kRenderAgain): the caller gets the static kernel's frame.  Called after a relay render, d_fb holding its frames. */
+int relay_seat_belt(curvis_ctx *ctx, const BruteCall &c) {
+  /* everything that shapes the hand-over pattern: frame size and count, metric and step flavour, the band, the step cap, the
+   * segment length and hop limit in force */
+  const std::array<uint32_t, 9> shape = {c.W, c.H, c.n_frames, (uint32_t)c.metric->kind, (uint32_t)(ctx->fast_math != 0 ? 1 : 0),
+                                         c.row_begin, c.row_count, c.max_iter,
+                                         (uint32_t)ctx->relay_segment * 256u + (uint32_t)std::max(0, ctx->relay_max_hops)};
+  bool auto_check = false;
+  if (!ctx->relay_verify && ctx->relay_auto_verify) {
+    const uint64_t seen = ctx->relay_verified[shape]++; /* relay launches of this shape before this one */
+    auto_check = seen == 0 || (ctx->relay_recheck_every > 0 && seen % (uint64_t)ctx->relay_recheck_every == 0);
+  }
+  if (!ctx->relay_verify && !auto_check) return CURVIS_OK;
+  /* the relay frame is kept in a second device buffer and compared there: no host copies (two pageable D2H copies of a
+   * batch cost more than the static re-render and left the NEXT render call 20 ms slower) */
+  const size_t fb_bytes = c.fb_bytes, padded = (fb_bytes + 7) & ~(size_t)7;
+  int rc = ctx->d_verify.reserve(ctx, padded + 8);
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_verify + (padded - 8), 0, 16, ctx->stream)); /* tail padding + the counter */
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_verify, ctx->d_fb, fb_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  if (ctx->d_fb.cap < padded) { /* room for the zeroed tail the word-wise compare reads (the frame is re-rendered below anyway) */
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = ctx->d_fb.reserve(ctx, padded))) return rc;
+  }
+  const LastRenderStats relay_run(ctx);
+  const int saved = ctx->variant;
+  ctx->variant = 1; /* the static kernel */
+  rc = render_again(ctx, c, false);
+  ctx->variant = saved;
+  if (rc) return rc;
+  /* d_fb holds the static kernel's frame now */
+  if (padded != fb_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->d_fb + fb_bytes, 0, padded - fb_bytes, ctx->stream));
+  unsigned long long *d_cnt = (unsigned long long *)(ctx->d_verify + padded);
+  const size_t n_words = padded / 8;
+  hipLaunchKernelGGL(compare_kernel, dim3((unsigned)std::min<size_t>((n_words + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                     (const unsigned long long *)ctx->d_verify.p, (const unsigned long long *)ctx->d_fb.p, n_words, d_cnt);
+  HIP_TRY(ctx, hipGetLastError());
+  unsigned long long n_diff_words = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&n_diff_words, d_cnt, sizeof n_diff_words, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  const std::vector<curvis_stats> &fs = relay_run.frames;
+  bool same = n_diff_words == 0 && fs.size() == ctx->last_frame_stats.size();
+  for (size_t f = 0; same && f < fs.size(); ++f) {
+    const curvis_stats &x = fs[f], &y = ctx->last_frame_stats[f];
+    same = x.rays == y.rays && x.steps == y.steps && x.n_pos == y.n_pos && x.n_neg == y.n_neg && x.n_none == y.n_none && x.n_oob == y.n_oob;
+  }
+  if (!same) {
+    ctx->relay_mismatches++;
+    if (ctx->relay_verify) return fail(ctx, CURVIS_E_HIP, "relay_verify: the relay kernel and the static kernel disagree on this launch");
+    fprintf(stderr, "[curvis] relay kernel: a checked launch of shape %ux%u x %u frame(s) differs from the static kernel (%llu of %zu 8-byte words%s); "
+                    "this context uses the static kernel from now on\n", c.W, c.H, c.n_frames, n_diff_words, n_words, n_diff_words ? "" : ", counters only");
+    ctx->relay_disabled = 1;
+    ctx->relay_fallbacks++;
+    return kRenderAgain;
+  }
+  ctx->relay_checks++;
+  /* the launch that counts is the relay one: its frame is what d_fb holds again (same bytes), and so are its statistics */
+  relay_run.restore(ctx);
+  return CURVIS_OK;
+}
+
+/* debug dump: x[0] of every ray.  Dead lanes of the integrator, replayed on the host: t_{k+1} = t_k + (p_t * g^tt) * delta with
+ * p_t = 1, g^tt = -1 (src/metrics.rs:237, :295); p_t = p_t + 0*delta stays 1. */
+void replay_debug_time(const BruteCall &c) {
+  std::vector<double> t_of_steps;
+  for (uint32_t f = 0; f < c.n_frames; ++f) {
+    curvis_ray_debug *d = c.dbg_out + (size_t)f * c.npix;
+    uint32_t most = 0; /* the table only needs to reach the largest step count of the frame, not the cap */
+    for (size_t i = 0; i < c.npix; ++i) most = std::max(most, d[i].steps);
+    t_of_steps.resize((size_t)most + 1);
+    double t = c.cams[f].pos[0];
+    t_of_steps[0] = t;
+    for (uint32_t k = 1; k <= most; ++k) {
+      t = t + (1.0 * -1.0) * c.delta;
+      t_of_steps[k] = t;
+    }
+    for (size_t i = 0; i < c.npix; ++i) d[i].x[0] = t_of_steps[d[i].steps];
+  }
+}
+
 int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames,
                 uint32_t max_iterations, double max_radius, double delta, uint8_t *rgb_out,
                 curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0, uint32_t row_count = 0) {
@@ -461,344 +757,66 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
   const auto t_begin = std::chrono::steady_clock::now();
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
-  const uint32_t W = cams[0].res_x, H_full = cams[0].res_y;
-  if (W == 0 || H_full == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
+  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count};
+  const uint32_t H_full = cams[0].res_y;
+  c.W = cams[0].res_x;
+  if (c.W == 0 || H_full == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
   /* row band (curvis_render_brute_rows): the launch covers image rows [row_begin, row_begin + row_count); the
    * cameras keep the full resolution, which is what pixel -> direction uses */
   const bool band = row_count != 0;
   if (band && ((uint64_t)row_begin + row_count > H_full || n_frames != 1 || dbg_out))
     return fail(ctx, CURVIS_E_INVALID, "row band outside the frame (or used with a batch / the debug dump)");
-  const uint32_t H = band ? row_count : H_full;
+  c.H = band ? row_count : H_full;
   for (uint32_t f = 0; f < n_frames; ++f) {
-    if (cams[f].res_x != W || cams[f].res_y != H_full)
+    if (cams[f].res_x != c.W || cams[f].res_y != H_full)
       return fail(ctx, CURVIS_E_INVALID, "all cameras of a batch must share one resolution");
     if (std::fabs(cams[f].pos[1]) > max_radius)
       return fail(ctx, CURVIS_E_CAMERA_OUTSIDE,
                   "Photon already beyond the maximum radius. Cannot evaluate escape. (src/systems.rs:122-124)");
   }
-  if (!ctx->d_sky[0] || !ctx->d_sky[1]) return fail(ctx, CURVIS_E_NO_SKY, "both background images must be set");
+  if (!ctx->sky[0].texels || !ctx->sky[1].texels) return fail(ctx, CURVIS_E_NO_SKY, "both background images must be set");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-  const size_t npix = (size_t)W * H;
-  const size_t fb_bytes = npix * 3 * n_frames;
-  rc = fb_begin_write(ctx, fb_bytes);
-  if (rc) return rc;
-  ctx->fb_bytes = fb_bytes;
-  if (dbg_out) {
-    rc = ensure_device(ctx, ctx->d_dbg, ctx->dbg_cap, npix * n_frames);
-    if (rc) return rc;
-  }
-  /* fused shading: static kernel, no debug dump (option "fuse_shade", default on) -- no ray store at all.
-   * Otherwise frames are rendered in chunks whose ray store stays below max_store_bytes. */
-  const bool fused = ctx->variant != 0 && ctx->fuse_shade != 0 && dbg_out == nullptr;
-  /* relay kernel ("variant" = 2, and the automatic choice for big enough single images): end-game hand-over of
-   * tiles; only launches of a few frames have a tail worth its staging area (56 B per ray) -- larger batches
-   * use the static kernel, and so do frames too small to have a dispatch phase (measured against the static
-   * kernel: 640x360 +2 %, 720x405 -9 %, 800x450 -9 %, 960x540 -15 %, 1280x720 -6 %, 1920x1080 -3..-5 %,
-   * 2560x1440 -1 %; tools/gpu_relay_sizes.py, tools/gpu_relay_threshold.py) */
-  const unsigned long long relay_fresh_blocks = ((unsigned long long)((W + 7) / 8) * ((H + 7) / 8) * n_frames + 3ull) / 4ull;
-  const unsigned long long relay_min = ctx->relay_min_blocks >= 0 ? (unsigned long long)ctx->relay_min_blocks
-                                                                   : 4ull * (unsigned long long)ctx->prop.multiProcessorCount;
-  const size_t relay_staging = (size_t)((W + 7) / 8) * ((H + 7) / 8) * 64u * n_frames * kStoreBytesPerPixel;
-  const bool relay = (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && fused && n_frames <= (uint32_t)ctx->relay_max_frames &&
-                     relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
-  uint32_t chunk = n_frames;
-  if (relay) {
-    const size_t rays = (size_t)((W + 7) / 8) * ((H + 7) / 8) * 64u * n_frames;
-    rc = ensure_device(ctx, ctx->d_store, ctx->store_cap, rays * kStoreBytesPerPixel);
-    if (rc) return rc;
-  }
-  if (!fused) {
-    chunk = (uint32_t)std::max<size_t>(1, ctx->max_store_bytes / (npix * kStoreBytesPerPixel));
-    if (chunk > n_frames) chunk = n_frames;
-    rc = ensure_device(ctx, ctx->d_store, ctx->store_cap, (size_t)chunk * npix * kStoreBytesPerPixel);
-    if (rc) return rc;
-  }
-  rc = ensure_device(ctx, ctx->d_cams, ctx->cams_cap, (size_t)n_frames);
-  if (rc) return rc;
-  if (ctx->h_cams_cap < n_frames) {
-    if (ctx->h_cams) HIP_TRY(ctx, hipHostFree(ctx->h_cams));
-    ctx->h_cams = nullptr;
-    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->h_cams, sizeof(cvk::CameraParams) * n_frames));
-    ctx->h_cams_cap = n_frames;
-  }
+  c.npix = (size_t)c.W * c.H;
+  c.fb_bytes = c.npix * 3 * n_frames;
+  if ((rc = fb_begin_write(ctx, c.fb_bytes))) return rc;
+  ctx->fb_bytes = c.fb_bytes;
+  if (dbg_out && (rc = ctx->d_dbg.reserve(ctx, c.npix * n_frames))) return rc;
+  const RenderPath path = choose_render_path(ctx, c);
+  if (path.store_bytes && (rc = ctx->d_store.reserve(ctx, path.store_bytes))) return rc;
+  if ((rc = ctx->d_cams.reserve(ctx, n_frames))) return rc;
+  if ((rc = ctx->h_cams.reserve(ctx, n_frames))) return rc;
   for (uint32_t f = 0; f < n_frames; ++f) ctx->h_cams[f] = make_camera(cams[f]);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, sizeof(cvk::CameraParams) * n_frames, hipMemcpyHostToDevice,
-                              ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, sizeof(cvk::CameraParams) * n_frames, hipMemcpyHostToDevice, ctx->stream));
 
   const cvk::MetricParams MP = make_metric(*metric);
-  const bool phi = dbg_out != nullptr; /* phi is only read by the debug dump on this path */
-  const bool fast = ctx->fast_math != 0;
-  uint64_t tot[FC_N] = {0};
-  double integrate_ms = 0.0, shade_ms = 0.0;
+  RenderTotals tot;
   ctx->last_frame_stats.assign(n_frames, curvis_stats{});
-
-  for (uint32_t f0 = 0; f0 < n_frames; f0 += chunk) {
-    const uint32_t nf = std::min(chunk, n_frames - f0);
-    FrameCounters FC;
-    rc = prepare_counters(ctx, nf, FC);
+  for (uint32_t f0 = 0; f0 < n_frames; f0 += path.chunk) {
+    rc = render_chunk(ctx, c, path, MP, f0, std::min(path.chunk, n_frames - f0), tot);
+    if (rc == kRenderAgain) return render_again(ctx, c, true);
     if (rc) return rc;
-    const size_t cnt_words = counter_words(nf, FC.slots);
-    IntegrateParams P;
-    P.metric = MP;
-    P.cams = ctx->d_cams + f0;
-    P.n_frames = nf;
-    P.W = W;
-    P.H = H;
-    P.row0 = band ? row_begin : 0u;
-    P.tiles_x = (W + 7) / 8;
-    P.tiles_y = (H + 7) / 8;
-    const unsigned long long rpf = (unsigned long long)P.tiles_x * P.tiles_y * 64ull;
-    if (rpf > 0xFFFFFFFFull || rpf * nf / 64ull > 0xFFFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
-    P.rays_per_frame = (unsigned)rpf;
-    P.total_rays = rpf * nf;
-    P.max_iter = max_iterations;
-    P.max_radius = max_radius;
-    P.delta = delta;
-    P.store = relay ? carve_store(ctx->d_store, (size_t)P.total_rays)
-                    : fused ? RayStore{} : carve_store(ctx->d_store, (size_t)nf * npix);
-    P.counters = FC;
-    for (int k = 0; k < 2; ++k) {
-      P.sky[k].texels = (const unsigned *)ctx->d_sky[k];
-      P.sky[k].w = ctx->sky_w[k];
-      P.sky[k].h = ctx->sky_h[k];
-      for (int i = 0; i < 9; ++i) P.sky[k].inv_rot[i] = ctx->sky_inv_rot[k][i];
-    }
-    P.fb = ctx->d_fb + (size_t)f0 * npix * 3;
-    P.refill_threshold = ctx->refill_threshold < 1 ? 1 : (ctx->refill_threshold > 64 ? 64 : ctx->refill_threshold);
-    P.fast_ok = cvk::metric_fast_ok(metric->kind, MP, max_radius) ? 1 : 0;
-    P.trace = nullptr;
-    const char *trace_file = getenv("CURVIS_TRACE_FILE");
-    const size_t trace_words = (size_t)(P.total_rays / 64ull) * 4u;
-    size_t trace_alloc_words = trace_words;
-    if (relay) trace_alloc_words = (size_t)(P.total_rays / 64ull) * 3u * 4u + 65536u * 16u; /* every wave of the grid */
-    if (trace_file && *trace_file && (ctx->variant != 0 || relay)) {
-      HIP_TRY(ctx, hipMalloc((void **)&P.trace, trace_alloc_words * sizeof(unsigned long long)));
-      HIP_TRY(ctx, hipMemsetAsync(P.trace, 0, trace_alloc_words * sizeof(unsigned long long), ctx->stream));
-    }
-
-    ShadeParams Q;
-    Q.metric = MP;
-    for (int k = 0; k < 2; ++k) {
-      Q.sky[k].texels = (const unsigned *)ctx->d_sky[k];
-      Q.sky[k].w = ctx->sky_w[k];
-      Q.sky[k].h = ctx->sky_h[k];
-      for (int i = 0; i < 9; ++i) Q.sky[k].inv_rot[i] = ctx->sky_inv_rot[k][i];
-    }
-    Q.store = P.store;
-    Q.n_pixels = (unsigned long long)nf * npix;
-    Q.fb = ctx->d_fb + (size_t)f0 * npix * 3;
-    Q.dbg = dbg_out ? ctx->d_dbg + (size_t)f0 * npix : nullptr;
-    Q.npix = npix;
-    Q.counters = FC;
-
-    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    rc = launch_integrate_any(ctx, metric->kind, phi, fast, fused, relay ? 1 : 0, P);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-    if (P.trace) { /* diagnostics only: dump the per-wave records of this launch (binary u64 x 4 per wave) */
-      std::vector<unsigned long long> tr(trace_alloc_words);
-      HIP_TRY(ctx, hipMemcpyAsync(tr.data(), P.trace, trace_alloc_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_TRY(ctx, hipFree(P.trace));
-      if (FILE *fp = fopen(trace_file, "wb")) {
-        fwrite(tr.data(), sizeof(unsigned long long), tr.size(), fp);
-        fclose(fp);
-      }
-    }
-    if (!fused) {
-      switch (metric->kind) {
-        case CURVIS_METRIC_ELLIS:
-          rc = launch_shade_kind<cvk::METRIC_ELLIS>(ctx, dbg_out != nullptr, Q);
-          break;
-        case CURVIS_METRIC_INTERSTELLAR:
-          rc = launch_shade_kind<cvk::METRIC_INTERSTELLAR>(ctx, dbg_out != nullptr, Q);
-          break;
-        default:
-          rc = launch_shade_kind<cvk::METRIC_FLAT>(ctx, dbg_out != nullptr, Q);
-          break;
-      }
-      if (rc) return rc;
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-    ctx->last_relay_launches = relay ? 1 : 0;
-    for (;;) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words,
-                                  hipMemcpyDeviceToHost, ctx->stream));
-      if (relay) /* queue header rides along with the counters: finished / error */
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters + cnt_words, ctx->d_rq, sizeof(unsigned long long) * 8,
-                                    hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      if (!relay) break;
-      /* normally the one launch finished every tile; more relay workgroups only if the grid ran out of them
-       * with tiles still parked */
-      const RelayQueue *hq = (const RelayQueue *)(ctx->h_counters + cnt_words);
-      const unsigned long long n_tiles = P.total_rays / 64ull;
-      if (hq->error != 0 || ctx->relay_test_fault) {
-        /* waves gave up waiting for a tile (a logic error, or a dispatcher that did not start the workgroups in
-         * order): not a hang and not a wrong frame -- the frame is rendered again by the static kernel, which has no
-         * inter-workgroup dependency, and this context stops using the relay kernel */
-        ctx->relay_test_fault = 0;
-        ctx->relay_disabled = 1;
-        ctx->relay_fallbacks++;
-        fprintf(stderr, "[curvis] relay kernel: %llu waves gave up waiting (%llu tiles unfinished); falling back to the static kernel for this context\n",
-                (unsigned long long)hq->error, (unsigned long long)(n_tiles - hq->finished));
-        return render_impl(ctx, metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin,
-                           row_count);
-      }
-      ctx->last_relay_parks = hq->tail;
-      ctx->last_relay_waiters = hq->head;
-      if (hq->finished >= n_tiles) break;
-      if (ctx->last_relay_launches++ > 64)
-        return fail(ctx, CURVIS_E_HIP, "relay kernel: tiles still unfinished after 64 relay launches");
-      rc = launch_integrate_any(ctx, metric->kind, phi, fast, fused, 2, P);
-      if (rc) return rc;
-      HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-      HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
-    }
-    float ms_i = 0.f, ms_s = 0.f;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms_i, ctx->ev0, ctx->ev1));
-    integrate_ms += ms_i;
-    HIP_TRY(ctx, hipEventElapsedTime(&ms_s, ctx->ev1, ctx->ev2));
-    shade_ms += ms_s;
-    for (uint32_t f = 0; f < nf; ++f) {
-      uint64_t fc[FC_N];
-      sum_frame_counters(ctx->h_counters, FC.slots, f, fc);
-      for (int k = 0; k < FC_N; ++k) tot[k] += fc[k];
-      curvis_stats &fs = ctx->last_frame_stats[f0 + f];
-      fs.rays = fc[FC_RAYS];
-      fs.steps = fc[FC_STEPS];
-      fs.n_pos = fc[FC_POS];
-      fs.n_neg = fc[FC_NEG];
-      fs.n_none = fc[FC_NONE];
-      fs.n_oob = fc[FC_OOB];
-      /* the frames of a launch run interleaved on the GPU: times are the launch's, shared out by executed steps */
-      fs.integrate_ms = ms_i;
-      fs.shade_ms = ms_s;
-    }
-    { /* time share of each frame of this launch, in proportion to its Euler steps */
-      uint64_t launch_steps = 0;
-      for (uint32_t f = 0; f < nf; ++f) launch_steps += ctx->last_frame_stats[f0 + f].steps;
-      for (uint32_t f = 0; f < nf; ++f) {
-        curvis_stats &fs = ctx->last_frame_stats[f0 + f];
-        const double share = launch_steps ? (double)fs.steps / (double)launch_steps : 1.0 / nf;
-        fs.integrate_ms *= share;
-        fs.shade_ms *= share;
-        fs.kernel_ms = fs.integrate_ms + fs.shade_ms;
-        fs.total_ms = fs.kernel_ms;
-      }
-    }
   }
-  ctx->last_integrate_ms = integrate_ms;
-  ctx->last_shade_ms = shade_ms;
-  /* The relay kernel's hand-over rests on gfx950 facts (write-through sc0 sc1 stores, s_waitcnt vmcnt(0) before
-   * the ticket store) rather than on the HIP memory model, so it wears a seat belt: the first relay launch of every
-   * launch shape is repeated by the static kernel -- no inter-workgroup traffic at all -- and frames and counters are
-   * compared.  Option "relay_verify" = 1 checks EVERY launch and makes a difference an error (debugging); the automatic
-   * check (option "relay_auto_verify", default 1) costs one static launch per shape and context and, on a difference,
-   * reports it on stderr, counts it ("relay_mismatches"), switches the context to the static kernel and returns the
-   * static kernel's frame. */
-  /* everything that shapes the hand-over pattern: frame size and count, metric and step flavour, the band, the step cap, the
-   * segment length and hop limit in force */
-  const std::array<uint32_t, 9> shape = {W, H, n_frames, (uint32_t)metric->kind, (uint32_t)(fast ? 1 : 0), row_begin, row_count, max_iterations,
-                                         (uint32_t)ctx->relay_segment * 256u + (uint32_t)std::max(0, ctx->relay_max_hops)};
-  bool auto_check = false;
-  if (relay && !ctx->relay_verify && ctx->relay_auto_verify) {
-    const uint64_t seen = ctx->relay_verified[shape]++; /* relay launches of this shape before this one */
-    auto_check = seen == 0 || (ctx->relay_recheck_every > 0 && seen % (uint64_t)ctx->relay_recheck_every == 0);
-  }
-  if (relay && (ctx->relay_verify || auto_check)) {
-    /* the relay frame is kept in a second device buffer and compared there: no host copies (two pageable D2H copies of a
-     * batch cost more than the static re-render and left the NEXT render call 20 ms slower) */
-    const size_t padded = (fb_bytes + 7) & ~(size_t)7;
-    rc = ensure_device(ctx, ctx->d_verify, ctx->verify_cap, padded + 8);
+  ctx->last_integrate_ms = tot.integrate_ms;
+  ctx->last_shade_ms = tot.shade_ms;
+  if (path.relay) {
+    rc = relay_seat_belt(ctx, c);
+    if (rc == kRenderAgain) return render_again(ctx, c, true);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_verify + (padded - 8), 0, 16, ctx->stream)); /* tail padding + the counter */
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_verify, ctx->d_fb, fb_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    if (ctx->fb_cap < padded) { /* room for the zeroed tail the word-wise compare reads (the frame is re-rendered below anyway) */
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      rc = ensure_device(ctx, ctx->d_fb, ctx->fb_cap, padded);
-      if (rc) return rc;
-    }
-    const std::vector<curvis_stats> fs = ctx->last_frame_stats;
-    const uint32_t launches = ctx->last_relay_launches;
-    const uint64_t parks = ctx->last_relay_parks, waiters = ctx->last_relay_waiters;
-    const double keep_i = ctx->last_integrate_ms, keep_s = ctx->last_shade_ms;
-    const int saved = ctx->variant;
-    ctx->variant = 1;
-    rc = render_impl(ctx, metric, cams, n_frames, max_iterations, max_radius, delta, nullptr, nullptr, nullptr, row_begin, row_count);
-    ctx->variant = saved;
-    if (rc) return rc;
-    /* d_fb holds the static kernel's frame now */
-    if (padded != fb_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->d_fb + fb_bytes, 0, padded - fb_bytes, ctx->stream));
-    unsigned long long *d_cnt = (unsigned long long *)(ctx->d_verify + padded);
-    const size_t n_words = padded / 8;
-    hipLaunchKernelGGL(compare_kernel, dim3((unsigned)std::min<size_t>((n_words + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)ctx->d_verify, (const unsigned long long *)ctx->d_fb, n_words, d_cnt);
-    HIP_TRY(ctx, hipGetLastError());
-    unsigned long long n_diff_words = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n_diff_words, d_cnt, sizeof n_diff_words, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    bool same = n_diff_words == 0 && fs.size() == ctx->last_frame_stats.size();
-    for (size_t f = 0; same && f < fs.size(); ++f) {
-      const curvis_stats &x = fs[f], &y = ctx->last_frame_stats[f];
-      same = x.rays == y.rays && x.steps == y.steps && x.n_pos == y.n_pos && x.n_neg == y.n_neg && x.n_none == y.n_none && x.n_oob == y.n_oob;
-    }
-    if (!same) {
-      ctx->relay_mismatches++;
-      if (ctx->relay_verify) return fail(ctx, CURVIS_E_HIP, "relay_verify: the relay kernel and the static kernel disagree on this launch");
-      fprintf(stderr, "[curvis] relay kernel: a checked launch of shape %ux%u x %u frame(s) differs from the static kernel (%llu of %zu 8-byte words%s); "
-                      "this context uses the static kernel from now on\n", W, H, n_frames, n_diff_words, n_words, n_diff_words ? "" : ", counters only");
-      ctx->relay_disabled = 1;
-      ctx->relay_fallbacks++;
-      return render_impl(ctx, metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count);
-    }
-    ctx->relay_checks++;
-    /* the launch that counts is the relay one: its frame is what d_fb holds again (same bytes), and so are its statistics */
-    ctx->last_frame_stats = fs;
-    ctx->last_relay_launches = launches;
-    ctx->last_relay_parks = parks;
-    ctx->last_relay_waiters = waiters;
-    ctx->last_integrate_ms = keep_i;
-    ctx->last_shade_ms = keep_s;
   }
   if (dbg_out)
-    HIP_TRY(ctx, hipMemcpyAsync(dbg_out, ctx->d_dbg, sizeof(curvis_ray_debug) * npix * n_frames,
-                                hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dbg_out, ctx->d_dbg, sizeof(curvis_ray_debug) * c.npix * n_frames, hipMemcpyDeviceToHost, ctx->stream));
   if (rgb_out) {
-    rc = fb_download(ctx, rgb_out, fb_bytes);
-    if (rc) return rc;
+    if ((rc = fb_download(ctx, rgb_out, c.fb_bytes))) return rc;
   } else {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  if (dbg_out) {
-    /* dead lanes of the integrator, replayed on the host: t_{k+1} = t_k + (p_t * g^tt) * delta with
-     * p_t = 1, g^tt = -1 (src/metrics.rs:237, :295); p_t = p_t + 0*delta stays 1. */
-    std::vector<double> t_of_steps;
-    for (uint32_t f = 0; f < n_frames; ++f) {
-      curvis_ray_debug *d = dbg_out + (size_t)f * npix;
-      uint32_t most = 0; /* the table only needs to reach the largest step count of the frame, not the cap */
-      for (size_t i = 0; i < npix; ++i) most = std::max(most, d[i].steps);
-      t_of_steps.resize((size_t)most + 1);
-      double t = cams[f].pos[0];
-      t_of_steps[0] = t;
-      for (uint32_t k = 1; k <= most; ++k) {
-        t = t + (1.0 * -1.0) * delta;
-        t_of_steps[k] = t;
-      }
-      for (size_t i = 0; i < npix; ++i) d[i].x[0] = t_of_steps[d[i].steps];
-    }
-  }
+  if (dbg_out) replay_debug_time(c);
   if (stats) {
-    stats->rays = tot[FC_RAYS];
-    stats->steps = tot[FC_STEPS];
-    stats->n_pos = tot[FC_POS];
-    stats->n_neg = tot[FC_NEG];
-    stats->n_none = tot[FC_NONE];
-    stats->n_oob = tot[FC_OOB];
-    stats->kernel_ms = integrate_ms + shade_ms;
-    stats->integrate_ms = integrate_ms;
-    stats->shade_ms = shade_ms;
+    counts_to_stats(tot.counts, *stats);
+    stats->kernel_ms = tot.integrate_ms + tot.shade_ms;
+    stats->integrate_ms = tot.integrate_ms;
+    stats->shade_ms = tot.shade_ms;
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   return CURVIS_OK;
