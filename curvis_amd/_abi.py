@@ -124,6 +124,7 @@ SYMBOLS = {
     "curvis_selftest_math": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_size_t]),
     "curvis_selftest_math3": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_size_t]),
     "curvis_selftest_fast_step": (C.c_int, [_vp, C.POINTER(Metric), C.c_double, C.c_double, _dp, C.c_size_t, _dp]),
+    "curvis_selftest_sky_indices": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _dp, _dp, C.c_size_t, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

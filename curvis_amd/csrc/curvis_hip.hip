@@ -28,6 +28,7 @@
  *   shade_kernel<KIND,DEBUG>               staged shading (persistent kernel, debug dump of every ray).
  *   escape_angle_kernel<KIND,FAST>, efficient_pixel_kernel, direct_kernel, trajectory_kernel   efficient mode and extras.
  *   selftest_math_kernel                   cv_math.h / IEEE div / sqrt / hardware seeds for the tests.
+ *   selftest_sky_indices_kernel            cvk::sky_indices (direction -> texel), both instantiations, on the tests' directions.
  *   FAST = shared-reciprocal Euler step (cv_device.h ray_step_fast), !FAST = compiler IEEE div/sqrt;
  *   PHI = integrate phi as well (debug dump, escape angles).
  *
@@ -991,6 +992,32 @@ int curvis_selftest_fast_step(curvis_ctx *ctx, const curvis_metric *metric, doub
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipMemcpy(out, dout, n * CURVIS_FAST_STEP_RECORD * sizeof(double), hipMemcpyDeviceToHost));
+  return CURVIS_OK;
+}
+
+int curvis_selftest_sky_indices(curvis_ctx *ctx, uint32_t w, uint32_t h, const double inv_rot[9], const double *dirs, size_t n,
+                                uint32_t *out) {
+  if (!ctx || !inv_rot || !dirs || !out) return CURVIS_E_INVALID;
+  if (n == 0) return CURVIS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  cvk::SkyParams S;
+  S.texels = nullptr; /* sky_indices does not read texels */
+  S.w = w;
+  S.h = h;
+  for (int i = 0; i < 9; ++i) S.inv_rot[i] = inv_rot[i];
+  /* y_pi, y_two_pi from where efficient_pixel_kernel's P.recips come from (they do not depend on the resolution: a cached one is kept) */
+  const curvis_ctx::PixRecips &cached = ctx->pix_recips;
+  cvk::PixelRecips R;
+  if (int rc = ensure_pixel_recips(ctx, cached.valid ? cached.res_x : 1.0, cached.valid ? cached.res_y : 1.0, R)) return rc;
+  DeviceBuffer<double> din;
+  DeviceBuffer<unsigned> dout;
+  if (int rc = din.reserve(ctx, n * 3)) return rc;
+  if (int rc = dout.reserve(ctx, n * 4)) return rc;
+  HIP_TRY(ctx, hipMemcpy(din, dirs, n * 3 * sizeof(double), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(selftest_sky_indices_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, S, R, din.p, n, dout.p);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, dout, n * 4 * sizeof(unsigned), hipMemcpyDeviceToHost));
   return CURVIS_OK;
 }
 

@@ -594,6 +594,22 @@ __global__ void selftest_math3_kernel(int op, const double *a, const double *b, 
   out[i] = r;
 }
 
+/* cvk::sky_indices on chosen directions (tests/test_gpu_sky_lookup.py): d = n x {d0, d1, d2}; out = n x {tx, ty of sky_indices<false>
+ * (the brute and direct renderers' epilogues), tx, ty of sky_indices<true> (the efficient pixel kernel's, R = the call's shared
+ * reciprocals)} -- raw, before the clamp.  S.texels is not read. */
+__global__ void selftest_sky_indices_kernel(cvk::SkyParams S, cvk::PixelRecips R, const double *d, size_t n, unsigned *out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double d0 = d[3 * i], d1 = d[3 * i + 1], d2 = d[3 * i + 2];
+  unsigned tx, ty;
+  cvk::sky_indices<false>(S, d0, d1, d2, tx, ty);
+  out[4 * i + 0] = tx;
+  out[4 * i + 1] = ty;
+  cvk::sky_indices<true>(S, d0, d1, d2, tx, ty, R.y_pi, R.y_two_pi);
+  out[4 * i + 2] = tx;
+  out[4 * i + 3] = ty;
+}
+
 /* One fast Euler step per input state with every quotient of the step recorded (cvk::NoProbe's counterpart): for
  * each state 6 x {numerator, denominator, the shared reciprocal the step used, the step's quotient, the IEEE
  * quotient, the remainder n - d RN(n y), 1 - d y} (NaN rows: quotient not formed -- k = 0 outside Ellis, or the state took the strict step), then the new

@@ -644,6 +644,17 @@ class Context:
               self._h)
         return out[:, :42].reshape(n, 6, 7), out[:, 42:47], out[:, 47:52], out[:, 52] != 0.0
 
+    def selftest_sky_indices(self, w, h, dirs, inv_rot=None):
+        """the sky lookup of the kernels on n directions (n x 3) for a w x h sky with inverse rotation inv_rot (default: identity):
+        a uint32 array [n, 4] = raw (tx, ty) of the brute / direct renderers, then of the efficient renderer's per-pixel kernel
+        (curvis_selftest_sky_indices); raw: before the clamp, so tx == w / ty == h can come back"""
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        inv = np.ascontiguousarray(np.eye(3) if inv_rot is None else inv_rot, dtype=np.float64).reshape(9)
+        out = np.zeros((d.shape[0], 4), dtype=np.uint32)
+        check(lib().curvis_selftest_sky_indices(self._h, int(w), int(h), dptr(inv), dptr(d), d.shape[0],
+                                                out.ctypes.data_as(C.POINTER(C.c_uint32))), self._h)
+        return out
+
 
 _default_ctx = {}
 

@@ -420,6 +420,14 @@ int curvis_selftest_math3(curvis_ctx *ctx, int op, const double *a, const double
 int curvis_selftest_fast_step(curvis_ctx *ctx, const curvis_metric *metric, double delta, double max_radius, const double *states,
                               size_t n, double *out);
 
+/* the sky lookup (direction -> texel indices, src/images.rs:115-174) as the kernels compile it, on chosen directions: a sky of
+ * w x h texels with inverse rotation inv_rot (row-major 3 x 3; no image is needed), dirs = n x {d0, d1, d2};
+ * out: n x {tx, ty as the brute and direct renderers compute them, tx, ty as the efficient renderer's per-pixel kernel does, with
+ * theta / pi and phi / 2 pi through the shared reciprocals an efficient render call of this context uses} -- raw `as u32`
+ * values, BEFORE the clamp to w - 1 / h - 1 (ty == h for a direction on the -z axis).  tests/test_gpu_sky_lookup.py. */
+int curvis_selftest_sky_indices(curvis_ctx *ctx, uint32_t w, uint32_t h, const double inv_rot[9], const double *dirs, size_t n,
+                                uint32_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -358,6 +358,9 @@ double cvo_squared_norm_cov(int fl, const cvo_metric *m, const double p_cov[4], 
 void cvo_sky_indices(int fl, const cvo_sky *s, const double v[3], uint32_t *x, uint32_t *y) {
   DISPATCH(fl, sky_indices, s, v, x, y);
 }
+void cvo_sky_indices_array(int fl, const cvo_sky *s, const double *v, size_t n, uint32_t *xy) {
+  for (size_t i = 0; i < n; ++i) cvo_sky_indices(fl, s, v + 3 * i, xy + 2 * i, xy + 2 * i + 1);
+}
 int cvo_sky_pixel(int fl, const cvo_sky *s, const double v[3], uint8_t rgba[4]) {
   return DISPATCH(fl, sky_pixel, s, v, rgba, NULL, NULL);
 }

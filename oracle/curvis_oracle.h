@@ -123,6 +123,8 @@ double cvo_squared_norm_cov(int fl, const cvo_metric *m, const double p_cov[4], 
 
 /* --- sky lookup (src/images.rs:107-174) --- */
 void cvo_sky_indices(int fl, const cvo_sky *s, const double v[3], uint32_t *x, uint32_t *y);
+/* cvo_sky_indices for n directions (v: n x 3) -> xy: n x {x, y}; s->rgba is not read (a sky without an image will do) */
+void cvo_sky_indices_array(int fl, const cvo_sky *s, const double *v, size_t n, uint32_t *xy);
 int cvo_sky_pixel(int fl, const cvo_sky *s, const double v[3], uint8_t rgba[4]); /* returns 1 if OOB (clamped) */
 
 /* --- per-pixel renderer (src/systems.rs:307-330) --- */

@@ -18,6 +18,45 @@ def make_skies(w=512, h=256, kind="check"):
     return skies.smooth(w, h, 128), skies.smooth(w, h, 32)
 
 
+def _salt_bytes(salt):
+    return np.array([salt & 255, (salt >> 8) & 255, (salt >> 16) & 255], np.uint8)
+
+
+def index_sky(w, h, salt=0):
+    """an h x w RGBA8 image whose colour IS the texel index: R = x & 255, G = y & 255, B = (x >> 8) | (y >> 8) << 4, each XOR-ed with
+    one byte of the 24-bit `salt` -- injective in (x, y) for w, h <= 4096, and two skies with different salts never give the same
+    colour for the same texel.  With such skies a pixel comparison is a texel-index comparison plus a which-sky comparison
+    (checker skies only show an index through 64-texel cells).  Black is some texel's colour too: capped rays are told apart by
+    n_none and by the oracle's own pixel."""
+    assert 1 <= w <= 4096 and 1 <= h <= 4096 and 0 <= salt < 1 << 24
+    x = np.arange(w, dtype=np.uint32)[None, :]
+    y = np.arange(h, dtype=np.uint32)[:, None]
+    img = np.empty((h, w, 4), np.uint8)
+    img[..., 0] = (x & 255) + 0 * y
+    img[..., 1] = (y & 255) + 0 * x
+    img[..., 2] = (x >> 8) | ((y >> 8) << 4)
+    img[..., :3] ^= _salt_bytes(salt)
+    img[..., 3] = 255
+    return img
+
+
+def texel_of(rgb, salt=0):
+    """inverse of index_sky: (x, y) of the texel(s) with colour rgb (an array [..., 3] of uint8, or one triple)"""
+    c = (np.asarray(rgb, dtype=np.uint8) ^ _salt_bytes(salt)).astype(np.uint32)
+    return c[..., 0] | ((c[..., 2] & 15) << 8), c[..., 1] | ((c[..., 2] >> 4) << 8)
+
+
+def describe_texel(rgb, shapes, salts):
+    """what a pixel of a frame rendered over index skies says: the (sky, tx, ty) it can have come from ("sky 0 (12, 7)"), for
+    the message of a failed comparison.  shapes: [(w, h) of sky 0, of sky 1]"""
+    hits = []
+    for k, ((w, h), salt) in enumerate(zip(shapes, salts)):
+        x, y = texel_of(rgb, salt)
+        if x < w and y < h:
+            hits.append("sky %d (%d, %d)" % (k, x, y))
+    return " or ".join(hits) if hits else "no texel of either sky %s" % (tuple(int(v) for v in rgb),)
+
+
 def scene(metric="ellis", res=(64, 36), pos=(0.0, 5.0, HALF_PI, 0.0), fwd=(-1.0, 0.0, 0.0), up=(0.0, 0.0, 1.0),
           focal=15.0, diag=43.0):
     """returns (oracle metric, oracle camera, product metric, product camera)"""

@@ -98,6 +98,7 @@ def lib():
     sig("cvo_vector_to_direction", None, [i32, MP, dp, dp, dp])
     sig("cvo_squared_norm_cov", d, [i32, MP, dp, dp])
     sig("cvo_sky_indices", None, [i32, SP, dp, C.POINTER(u32), C.POINTER(u32)])
+    sig("cvo_sky_indices_array", None, [i32, SP, dp, C.c_size_t, C.POINTER(u32)])
     sig("cvo_sky_pixel", i32, [i32, SP, dp, C.POINTER(C.c_uint8)])
     sig("cvo_render_image", i32, [i32, MP, CP, SP, SP, u32, d, d, u32, u32, vp, vp, C.POINTER(Stats)])
     sig("cvo_compute_escape_angle", i32, [i32, MP, d, d, d, u32, d, dp, C.POINTER(u32)])
@@ -157,6 +158,25 @@ def sky(rgba, inv_rot=None):
         s.inv_rot[i] = m[i]
     s._keep = rgba
     return s
+
+
+def sky_shape(w, h, inv_rot=None):
+    """a Sky of w x h texels WITHOUT an image: for cvo_sky_indices / sky_indices_array only, which never read texels"""
+    s = Sky()
+    s.rgba = None
+    s.w, s.h = int(w), int(h)
+    m = np.eye(3).ravel() if inv_rot is None else np.asarray(inv_rot, dtype=np.float64).ravel()
+    for i in range(9):
+        s.inv_rot[i] = m[i]
+    return s
+
+
+def sky_indices_array(fl, s, dirs):
+    """cvo_sky_indices for n directions (n x 3): uint32 [n, 2] = raw (x, y), before any clamp"""
+    d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros((d.shape[0], 2), dtype=np.uint32)
+    lib().cvo_sky_indices_array(fl, C.byref(s), _dp(d), d.shape[0], out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    return out
 
 
 def render_image(fl, metric, cam, sky_pos, sky_neg, max_iter, max_radius, delta, row_begin=0, row_step=1,
