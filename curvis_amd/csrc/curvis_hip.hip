@@ -27,6 +27,9 @@
  *       Selectable ("variant" = 0); measured 3-8 % slower than the static kernel on every workload tried.
  *   shade_kernel<KIND,DEBUG>               staged shading (persistent kernel, debug dump of every ray).
  *   escape_angle_kernel<KIND,FAST>, efficient_pixel_kernel, direct_kernel, trajectory_kernel   efficient mode and extras.
+ *   geodesic_static / geodesic_relay / direct_kernel<..., SS>, efficient_pixel_ss_kernel<SS>   option "supersample" = SS in
+ *       {2, 4, 8} (SS = 1: the kernels above): the same kernels over the SS times finer ray grid; the wave that holds an 8x8 tile of it averages every SS x SS
+ *       block across its lanes (DPP / ds_swizzle / ds_bpermute) and stores one pixel per block (resolve_store).
  *   selftest_math_kernel                   cv_math.h / IEEE div / sqrt / hardware seeds for the tests.
  *   selftest_sky_indices_kernel            cvk::sky_indices (direction -> texel), both instantiations, on the tests' directions.
  *   FAST = shared-reciprocal Euler step (cv_device.h ray_step_fast), !FAST = compiler IEEE div/sqrt;
@@ -876,6 +879,12 @@ const OptionEntry kOptions[] = {
     {"relay_test_fault", nullptr, OPT_WRITE(relay_test_fault, int)},     /* consumed by render_chunk's re-launch loop */
     OPT_RW(fast_math, int),
     OPT_RW(fuse_shade, int),
+    {"supersample", OPT_READ(c->supersample),
+     [](curvis_ctx *c, int64_t v) -> int { /* divisors of 8: a pixel's rays then sit in one wave's 8x8 tile (resolve_store) */
+       if (v != 1 && v != 2 && v != 4 && v != 8) return fail(c, CURVIS_E_INVALID, "supersample must be 1, 2, 4 or 8");
+       c->supersample = (int)v;
+       return CURVIS_OK;
+     }},
     OPT_RW(device_sampler, int),
     {"device_sampler_min_frames", OPT_READ(c->device_sampler_min_frames),
      [](curvis_ctx *c, int64_t v) -> int {

@@ -15,6 +15,7 @@ struct EfficientCall {
   double max_radius, delta;
   uint32_t alpha_nums, max_iterations_sampling;
   double thr1, thr2;
+  uint32_t ss = 1; /* supersampling factor: with ss > 1 `cams` are those of the ss times finer pixel grid (render_efficient_impl) */
 };
 
 /* evaluate compute_escape_angle for a batch on the GPU */
@@ -138,6 +139,24 @@ int make_pixel_params(curvis_ctx *ctx, uint32_t n_frames, uint32_t W, uint32_t H
   Q.counters = FC;
   Q.w_magic = W > 1u ? ~0ull / W + 1ull : 0ull; /* floor((2^64 - 1) / W) + 1 = floor(2^64 / W) + 1 unless W divides 2^64, where it is 2^64 / W: exact too */
   return ensure_pixel_recips(ctx, (double)W, (double)H, Q.recips);
+}
+
+/* K3 over n_frames frames of Q.W x Q.H pixels: linear pixel order, or -- supersampled -- 8x8 tiles of the fine grid, four per workgroup */
+int launch_pixel_kernel(curvis_ctx *ctx, const EfficientPixelParams &Q, uint32_t n_frames, uint32_t ss) {
+  if (ss > 1u) {
+    const unsigned long long tiles = (unsigned long long)((Q.W + 7u) / 8u) * ((Q.H + 7u) / 8u);
+    if ((tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
+    with_supersample(ss, [&](auto N) {
+      constexpr int SS = decltype(N)::value;
+      if constexpr (SS > 1)
+        hipLaunchKernelGGL(efficient_pixel_ss_kernel<SS>, dim3((unsigned)((tiles + 3ull) / 4ull), n_frames), dim3(256), 0, ctx->stream, Q);
+    });
+  } else {
+    const size_t npix = (size_t)Q.W * Q.H;
+    hipLaunchKernelGGL(efficient_pixel_kernel, dim3((unsigned)((npix + 255) / 256), n_frames), dim3(256), 0, ctx->stream, Q);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return CURVIS_OK;
 }
 
 /* per-frame and total statistics of an efficient render from the mirrored counters, the sampling and per-pixel kernel times and
@@ -435,7 +454,7 @@ int render_efficient_device(curvis_ctx *ctx, const EfficientCall &c, const cvk::
     for (uint32_t f = 0; f < n_frames; ++f) cp[f] = make_camera(c.cams[f]);
     std::memcpy(stage + o_fr, eframes.data(), sizeof(cvk::EfficientFrame) * n_frames);
   }
-  const size_t fb_bytes = npix * 3 * n_frames;
+  const size_t fb_bytes = (size_t)(W / c.ss) * (H / c.ss) * 3 * n_frames; /* W x H: the (fine) pixel grid; frames are W/ss x H/ss */
   rc = fb_begin_write(ctx, fb_bytes);
   if (rc) return rc;
   ctx->fb_bytes = fb_bytes;
@@ -449,8 +468,7 @@ int render_efficient_device(curvis_ctx *ctx, const EfficientCall &c, const cvk::
   const PixelInputs in = {ctx->d_eff, o_cams, o_fr, S.d, S.o_tab_off, S.o_tab_n, S.o_grid_off, S.o_grid, S.o_tab[0], S.o_tab[3],
                           S.o_tab[4], S.o_tab[5], S.o_tab[6]};
   if ((rc = make_pixel_params(ctx, n_frames, W, H, FC, in, Q))) return rc;
-  hipLaunchKernelGGL(efficient_pixel_kernel, dim3((unsigned)((npix + 255) / 256), n_frames), dim3(256), 0, ctx->stream, Q);
-  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words, hipMemcpyDeviceToHost, ctx->stream));
   const auto t_launched = std::chrono::steady_clock::now();
@@ -775,7 +793,7 @@ int render_pixels_staged(curvis_ctx *ctx, const EfficientCall &c, const std::vec
   /* device buffers for K3 */
   const size_t npix = (size_t)W * H;
   if (npix > 0xFFFFFFFFull || n_frames > 65535u) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
-  const size_t fb_bytes = npix * 3 * n_frames;
+  const size_t fb_bytes = (size_t)(W / c.ss) * (H / c.ss) * 3 * n_frames; /* W x H: the (fine) pixel grid; frames are W/ss x H/ss */
   int rc = fb_begin_write(ctx, fb_bytes);
   if (rc) return rc;
   ctx->fb_bytes = fb_bytes;
@@ -815,8 +833,7 @@ int render_pixels_staged(curvis_ctx *ctx, const EfficientCall &c, const std::vec
   const PixelInputs in = {ctx->d_eff, o_cams, o_fr, ctx->d_eff, o_to, o_tn, o_go, o_gr, o_sx, o_me, o_ce, o_ms, o_cs};
   if ((rc = make_pixel_params(ctx, n_frames, W, H, FC, in, Q))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  hipLaunchKernelGGL(efficient_pixel_kernel, dim3((unsigned)((npix + 255) / 256), n_frames), dim3(256), 0, ctx->stream, Q);
-  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words,
                               hipMemcpyDeviceToHost, ctx->stream));
@@ -832,13 +849,22 @@ int render_pixels_staged(curvis_ctx *ctx, const EfficientCall &c, const std::vec
   return CURVIS_OK;
 }
 
-int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &c, uint8_t *rgb_out, curvis_stats *stats) {
+int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *rgb_out, curvis_stats *stats) {
+  if (!ctx) return CURVIS_E_INVALID;
+  if (!call.metric || !call.cams || call.n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
+  /* option "supersample" = N > 1: the call over the N times finer pixel grid (the samplers see camera radii only and do not notice),
+   * averaged into res_x x res_y frames by the per-pixel kernel; "rays" are fine pixels */
+  EfficientCall c = call;
+  std::vector<curvis_camera> fine;
+  if (ctx->supersample > 1) {
+    c.ss = (uint32_t)ctx->supersample;
+    if (!supersampled_cameras(call.cams, call.n_frames, c.ss, fine)) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
+    c.cams = fine.data();
+  }
   const curvis_metric *metric = c.metric;
   const curvis_camera *cams = c.cams;
   const uint32_t n_frames = c.n_frames, alpha_nums = c.alpha_nums;
   const double max_radius = c.max_radius;
-  if (!ctx) return CURVIS_E_INVALID;
-  if (!metric || !cams || n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   const auto t_begin = std::chrono::steady_clock::now();
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
@@ -910,6 +936,13 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   const auto t_begin = std::chrono::steady_clock::now();
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
+  /* option "supersample" = N > 1: the camera of the N times finer grid, averaged into res_x x res_y by the kernel's epilogue */
+  const uint32_t ss = (uint32_t)ctx->supersample;
+  std::vector<curvis_camera> fine;
+  if (ss > 1u) {
+    if (!supersampled_cameras(cam, 1, ss, fine)) return fail(ctx, CURVIS_E_INVALID, "frame too large");
+    cam = fine.data();
+  }
   const uint32_t W = cam->res_x, H = cam->res_y;
   if (W == 0 || H == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
   if (std::fabs(cam->pos[1]) > max_radius)
@@ -932,7 +965,7 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   P.max_radius = max_radius;
   P.delta = delta;
   P.fast_ok = cvk::metric_fast_ok(metric->kind, P.metric, max_radius) ? 1 : 0;
-  const size_t npix = (size_t)W * H, fb_bytes = npix * 3;
+  const size_t fb_bytes = (size_t)(W / ss) * (H / ss) * 3;
   rc = fb_begin_write(ctx, fb_bytes);
   if (rc) return rc;
   ctx->fb_bytes = fb_bytes;
@@ -945,8 +978,12 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   with_kind(metric->kind, [&](auto K) {
     with_flag(ctx->fast_math != 0, [&](auto F) {
-      hipLaunchKernelGGL((direct_kernel<decltype(K)::value, decltype(F)::value>), dim3((unsigned)((P.total_rays + 255ull) / 256ull)), dim3(256), 0,
-                         ctx->stream, P);
+      with_supersample(ss, [&](auto N) {
+        constexpr int KIND = decltype(K)::value, SS = decltype(N)::value;
+        constexpr bool FAST = decltype(F)::value;
+        const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
+        hipLaunchKernelGGL((direct_kernel<KIND, FAST, SS>), grid, dim3(256), 0, ctx->stream, P);
+      });
     });
   });
   HIP_TRY(ctx, hipGetLastError());

@@ -16,7 +16,9 @@ struct Args {
   int png_level = -1; /* -1 = the fast PNG writer (png_io.h; the reference's image crate also saves with its fast setting), 0..9 = zlib */
   int encode_bench = 0; /* video, diagnostics: every rendered frame is encoded this many extra times into a scratch file */
   std::string gpu_png = "auto"; /* video: PNG front end on the device (curvis_ctx_deflate_frames): auto = with the fast writer, on, off */
+  int supersample = 1; /* rays per pixel and axis, averaged on the device (library option "supersample"): 1, 2, 4 or 8 */
 };
+int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(code);
@@ -30,7 +32,7 @@ void usage() {
       "  common: [-m|--metric-settings <TOML FILE>] [-c|--camera-settings <TOML FILE>] [-s|--simulation-settings <TOML FILE>]\n"
       "  extensions: [--mode efficient|brute|direct] [--device N] [--devices N] [--batch B] [--stats FILE]\n"
       "              [--sky-broadcast rccl|upload] [--writers T] [--resume] [--png-level -1..9] [--gpu-png auto|on|off]\n"
-      "              [--contexts-per-device C]\n");
+      "              [--contexts-per-device C] [--supersample 1|2|4|8]\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -74,6 +76,11 @@ Args parse_args(int argc, char **argv) {
     else if (key == "--png-level") { take(val); a.png_level = std::max(-1, std::min(9, std::atoi(val.c_str()))); }
     else if (key == "--encode-bench") { take(val); a.encode_bench = std::max(0, std::atoi(val.c_str())); }
     else if (key == "--gpu-png") take(a.gpu_png);
+    else if (key == "--supersample") {
+      take(val);
+      if (val != "1" && val != "2" && val != "4" && val != "8") die("error: --supersample must be 1, 2, 4 or 8", 2);
+      a.supersample = g_supersample = std::atoi(val.c_str());
+    }
     else if (key == "-h" || key == "--help") { usage(); std::exit(0); }
     else if (!s.empty() && s[0] == '-') die("error: unexpected argument '" + s + "' found", 2);
     else pos.push_back(s);
@@ -220,6 +227,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
         die("error: CURVIS_CTX_OPTIONS: cannot set `" + kv + "`", 2);
     }
   }
+  if (g_supersample != 1) check(curvis_ctx_set_option(ctx, "supersample", g_supersample), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {

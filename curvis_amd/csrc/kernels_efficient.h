@@ -371,6 +371,68 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
   }
 }
 
+/* K3 with supersampling (option "supersample" = SS in {2, 4, 8}): P.W x P.H, the cameras and the shared reciprocals are those of
+ * the SS times finer grid, and fine pixels are enumerated by 8x8 tiles -- one per wave, four per workgroup, the frame in blockIdx.y --
+ * instead of linearly, so that the wave holding a tile averages its SS x SS blocks into the W/SS x H/SS frame (resolve_store,
+ * kernels_geodesic.h).  Per fine pixel it is efficient_pixel_kernel: the same interpolation, the same wave-level sky branches, the
+ * same per-workgroup statistics (counted in fine pixels). */
+template <int SS>
+__global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const EfficientPixelParams P) {
+  __shared__ unsigned s_cnt[5];
+  const unsigned f = blockIdx.y;
+  const unsigned tiles_x = (P.W + 7u) >> 3;
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned tile = blockIdx.x * 4u + wave; /* < 2^32: the grid is sized from the tile count on the host */
+  const unsigned tyi = tile / tiles_x, txi = tile - tyi * tiles_x;
+  const unsigned px = txi * 8u + (lane & 7u), py = tyi * 8u + (lane >> 3);
+  const bool valid = px < P.W && py < P.H; /* tiles past the last row have py >= H */
+  if (threadIdx.x < 5u) s_cnt[threadIdx.x] = 0u;
+  bool pos = false, neg = false, none = false, oob = false;
+  unsigned texel = 0xFF000000u;
+  if (valid) {
+    const unsigned off = P.tab_off[f], n = P.tab_n[f];
+    double fin[3], space;
+    cvk::efficient_pixel<true>(P.cams[f], P.frames[f], px, py, P.sx + off, P.m_e + off, P.c_e + off, P.m_s + off, P.c_s + off, n, fin, space,
+                               &P.recips, P.grid + P.grid_off[f]);
+    pos = (space == 1.0);
+    neg = (space == -1.0);
+    none = !(pos || neg);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { /* one sky after the other, each under its own branch: see efficient_pixel_kernel */
+      if (k == 0 ? pos : neg) {
+        const cvk::SkyParams &S = P.sky[k];
+        unsigned tx, ty;
+        cvk::sky_indices<true>(S, fin[0], fin[1], fin[2], tx, ty, P.recips.y_pi, P.recips.y_two_pi);
+        if (tx >= S.w || ty >= S.h) oob = true;
+        if (tx >= S.w) tx = S.w - 1;
+        if (ty >= S.h) ty = S.h - 1;
+        texel = S.texels[(size_t)ty * S.w + tx];
+      }
+    }
+  }
+  resolve_store<SS>(P.fb, P.W, P.H, f, px, py, valid, texel);
+  const unsigned long long vm = __builtin_amdgcn_ballot_w64(valid);
+  const unsigned n_pos = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(pos)), n_neg = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(neg));
+  const unsigned n_none = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(none)), n_oob = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(oob));
+  __syncthreads(); /* s_cnt cleared */
+  if (lane == 0u && vm) {
+    atomicAdd(&s_cnt[0], (unsigned)__popcll(vm));
+    if (n_pos) atomicAdd(&s_cnt[1], n_pos);
+    if (n_neg) atomicAdd(&s_cnt[2], n_neg);
+    if (n_none) atomicAdd(&s_cnt[3], n_none);
+    if (n_oob) atomicAdd(&s_cnt[4], n_oob);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0u && s_cnt[0]) {
+    unsigned long long *c = frame_counter_line(P.counters, f);
+    atomicAdd(&c[FC_RAYS], (unsigned long long)s_cnt[0]);
+    if (s_cnt[1]) atomicAdd(&c[FC_POS], (unsigned long long)s_cnt[1]);
+    if (s_cnt[2]) atomicAdd(&c[FC_NEG], (unsigned long long)s_cnt[2]);
+    if (s_cnt[3]) atomicAdd(&c[FC_NONE], (unsigned long long)s_cnt[3]);
+    if (s_cnt[4]) atomicAdd(&c[FC_OOB], (unsigned long long)s_cnt[4]);
+  }
+}
+
 /* "direct" mode (NOT in the reference; SURVEY 8f N1 names it as a quality option): what render_image_efficient
  * approximates by sampling + interpolation, computed exactly -- compute_escape_angle(l_cam, alpha) for the alpha of
  * EVERY pixel (src/systems.rs:203-261 on the result of :405-433), then step 5 (:498-523) with that escape angle and
@@ -390,9 +452,12 @@ struct DirectParams {
   FrameCounters counters;
 };
 
-template <int KIND, bool FAST>
+/* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
+template <int KIND, bool FAST, int SS = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 4 : 6)))
 void direct_kernel(const DirectParams P) {
+  [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */
+  if constexpr (SS > 1) texel_ss = 0xFF000000u;
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -439,11 +504,16 @@ void direct_kernel(const DirectParams P) {
     } else {
       none = 1;
     }
-    unsigned char *dst = P.fb + ((size_t)py * P.W + px) * 3;
-    dst[0] = (unsigned char)(texel & 0xFF);
-    dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-    dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+    if constexpr (SS == 1) {
+      unsigned char *dst = P.fb + ((size_t)py * P.W + px) * 3;
+      dst[0] = (unsigned char)(texel & 0xFF);
+      dst[1] = (unsigned char)((texel >> 8) & 0xFF);
+      dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+    } else {
+      texel_ss = texel;
+    }
   }
+  if constexpr (SS > 1) resolve_store<SS>(P.fb, P.W, P.H, 0u, px, py, valid, texel_ss);
   flush_frame_counts(P.counters, 0u, valid, steps, 1u, pos, neg, none, oob);
 }
 

@@ -252,6 +252,52 @@ __device__ __forceinline__ unsigned shade_ray(const cvk::MetricParams &M, const 
   return texel;
 }
 
+/* ---- supersampling (option "supersample" = SS in {2, 4, 8}): the launch runs over the SS x SS times finer ray grid, and the
+ * wave that holds an 8x8 tile of it averages every SS x SS block into one output pixel.  SS divides 8, so a block never straddles
+ * two waves: no atomics, no second pass.  Lane k of a tile is sub-pixel (k & 7, k >> 3), so the lanes of a block differ in the low
+ * log2 SS bits of each half of the lane number: xor masks {1, 8}, {1, 2, 8, 16}, {1, 2, 4, 8, 16, 32}.
+ *
+ * v of lane (lane ^ MASK).  Every lane of the wave must be active: DPP for the masks that stay inside a row of 16 lanes
+ * (quad_perm [1,0,3,2] and [2,3,0,1], row_ror:8), ds_swizzle in bit mode (and 0x1f, xor MASK) inside a half wave, ds_bpermute
+ * across the two halves -- none of them touches LDS memory. */
+template <unsigned MASK>
+__device__ __forceinline__ unsigned lane_xor(unsigned v) {
+  static_assert(MASK == 1u || MASK == 2u || MASK == 4u || MASK == 8u || MASK == 16u || MASK == 32u, "one bit of the lane number");
+  if (MASK == 1u) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
+  if (MASK == 2u) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);
+  if (MASK == 8u) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);
+  if (MASK == 4u || MASK == 16u) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, (int)((MASK << 10) | 0x1Fu));
+  return (unsigned)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 63u) ^ 32u) << 2), (int)v);
+}
+
+/* Called by EVERY lane of a wave that holds one 8x8 tile of the fine grid: (px, py) is the lane's fine pixel inside the launch,
+ * W x H the fine size of the launch (multiples of SS), `texel` what the lane's ray saw; lanes with !valid (outside the frame: whole
+ * blocks of them, since SS divides 8) add nothing.  Channel sums are at most 64 x 255 < 2^14: red and green share a dword.  The
+ * lane of sub-pixel (0, 0) of each block stores out = (sum + SS^2 / 2) >> (2 log2 SS) -- the straight average of the 8-bit values,
+ * half rounded up -- at pixel (px / SS, py / SS) of frame `frame` of the W/SS x H/SS frames in fb. */
+template <int SS>
+__device__ __forceinline__ void resolve_store(unsigned char *fb, unsigned W, unsigned H, unsigned frame, unsigned px, unsigned py,
+                                              bool valid, unsigned texel) {
+  static_assert(SS == 2 || SS == 4 || SS == 8, "a wave's 64 rays are an 8x8 tile: the factor must divide 8");
+  constexpr unsigned LG = SS == 2 ? 1u : SS == 4 ? 2u : 3u;
+  unsigned rg = valid ? ((texel & 0xFFu) | ((texel & 0xFF00u) << 8)) : 0u;
+  unsigned b = valid ? ((texel >> 16) & 0xFFu) : 0u;
+  rg += lane_xor<1>(rg), b += lane_xor<1>(b);
+  if (SS >= 4) rg += lane_xor<2>(rg), b += lane_xor<2>(b);
+  if (SS >= 8) rg += lane_xor<4>(rg), b += lane_xor<4>(b);
+  rg += lane_xor<8>(rg), b += lane_xor<8>(b);
+  if (SS >= 4) rg += lane_xor<16>(rg), b += lane_xor<16>(b);
+  if (SS >= 8) rg += lane_xor<32>(rg), b += lane_xor<32>(b);
+  if (valid && ((px | py) & (unsigned)(SS - 1)) == 0u) {
+    constexpr unsigned HALF = (unsigned)(SS * SS) / 2u;
+    const unsigned Wo = W >> LG, Ho = H >> LG;
+    unsigned char *dst = fb + ((size_t)frame * Wo * Ho + (size_t)(py >> LG) * Wo + (px >> LG)) * 3;
+    dst[0] = (unsigned char)(((rg & 0xFFFFu) + HALF) >> (2u * LG));
+    dst[1] = (unsigned char)(((rg >> 16) + HALF) >> (2u * LG));
+    dst[2] = (unsigned char)((b + HALF) >> (2u * LG));
+  }
+}
+
 /* K1, persistent form: lanes draw rays from a global queue with one wave-aggregated atomic whenever
  * `refill_threshold` lanes are free; terminated rays are stored together at that point. */
 template <int KIND, bool PHI, bool FAST>
@@ -330,10 +376,13 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
 /* K1, static form: one ray per thread, hardware block scheduling does the load balancing.
  * FUSED: the epilogue shades the pixel itself (direction, sky lookup, RGB8 store) instead of staging the
  * final state in HBM for shade_kernel -- the epilogue needs fewer registers than the loop, so the fusion is
- * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame. */
-template <int KIND, bool PHI, bool FAST, bool FUSED>
+ * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame.
+ * SS: supersampling factor (1: one ray per output pixel; 2, 4, 8: P is in units of the fine grid and the epilogue averages,
+ * resolve_store above; FUSED only). */
+template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
 void geodesic_static(const IntegrateParams P) {
+  static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -385,20 +434,32 @@ void geodesic_static(const IntegrateParams P) {
   const unsigned long long id2 = (unsigned long long)bid * blockDim.x + threadIdx.x;
   valid = id2 < P.total_rays && decode_ray(P, id2, frame, px, py);
   const size_t slot = valid ? (size_t)frame * P.W * P.H + (size_t)py * P.W + px : 0;
-  if (valid) {
-    if (FUSED) {
+  if constexpr (SS == 1) {
+    if (valid) {
+      if (FUSED) {
+        unsigned tx, ty;
+        const unsigned texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
+        unsigned char *dst = P.fb + slot * 3;
+        dst[0] = (unsigned char)(texel & 0xFF);
+        dst[1] = (unsigned char)((texel >> 8) & 0xFF);
+        dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+        pos = (code == cvk::CODE_POS);
+        neg = (code == cvk::CODE_NEG);
+        none = (code == cvk::CODE_NONE);
+      } else {
+        store_ray<PHI>(P.store, slot, q, steps, code);
+      }
+    }
+  } else {
+    unsigned texel = 0u;
+    if (valid) {
       unsigned tx, ty;
-      const unsigned texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
-      unsigned char *dst = P.fb + slot * 3;
-      dst[0] = (unsigned char)(texel & 0xFF);
-      dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-      dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+      texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
       pos = (code == cvk::CODE_POS);
       neg = (code == cvk::CODE_NEG);
       none = (code == cvk::CODE_NONE);
-    } else {
-      store_ray<PHI>(P.store, slot, q, steps, code);
     }
+    resolve_store<SS>(P.fb, P.W, P.H, frame, px, py, valid, texel); /* the whole wave: lanes outside the frame add nothing */
   }
   /* statistics of the wave's tile go to the counters of ITS frame (a tile never straddles frames); on the staged
    * path shade_kernel keeps them */
@@ -471,7 +532,7 @@ __device__ __forceinline__ T ld_sys(const T *p) { return __hip_atomic_load(const
 
 /* register budget: the Interstellar instantiation must stay at 5 waves per SIMD (<= 96 VGPRs; its LDS tables allow
  * no more anyway): left alone the allocator takes 97 and drops to four (+6 % time) */
-template <int KIND, bool FAST>
+template <int KIND, bool FAST, int SS = 1> /* SS: supersampling factor, as in geodesic_static */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
 void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
   __shared__ MathTablesLds<KIND> s_tab;
@@ -620,18 +681,31 @@ void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
     /* pixel position decoded again from the laundered tile number rather than kept live across the loop */
     unsigned tile_s = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)tile);
     asm volatile("" : "+s"(tile_s));
-    unsigned frame2, px2, py2;
     const unsigned long long id2 = (unsigned long long)tile_s * 64ull + lane;
-    if (id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2)) {
-      unsigned tx, ty;
-      const unsigned texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
-      unsigned char *dst = P.fb + ((size_t)frame2 * P.W * P.H + (size_t)py2 * P.W + px2) * 3;
-      dst[0] = (unsigned char)(texel & 0xFF);
-      dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-      dst[2] = (unsigned char)((texel >> 16) & 0xFF);
-      pos = (code == cvk::CODE_POS);
-      neg = (code == cvk::CODE_NEG);
-      none = (code == cvk::CODE_NONE);
+    if constexpr (SS == 1) {
+      unsigned frame2, px2, py2;
+      if (id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2)) {
+        unsigned tx, ty;
+        const unsigned texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
+        unsigned char *dst = P.fb + ((size_t)frame2 * P.W * P.H + (size_t)py2 * P.W + px2) * 3;
+        dst[0] = (unsigned char)(texel & 0xFF);
+        dst[1] = (unsigned char)((texel >> 8) & 0xFF);
+        dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+        pos = (code == cvk::CODE_POS);
+        neg = (code == cvk::CODE_NEG);
+        none = (code == cvk::CODE_NONE);
+      }
+    } else { /* the wave that finishes a tile holds all 64 of its rays, parked on the way or not: it averages them */
+      unsigned frame2 = 0, px2 = 0, py2 = 0, texel = 0u;
+      const bool valid2 = id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2);
+      if (valid2) {
+        unsigned tx, ty;
+        texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
+        pos = (code == cvk::CODE_POS);
+        neg = (code == cvk::CODE_NEG);
+        none = (code == cvk::CODE_NONE);
+      }
+      resolve_store<SS>(P.fb, P.W, P.H, frame2, px2, py2, valid2, texel);
     }
     if (lane == 0 && tile < A.n_tiles) atomicAdd(&Q->finished, 1ull);
   }

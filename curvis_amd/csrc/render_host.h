@@ -75,7 +75,7 @@ struct curvis_ctx {
                                        once, there is no dispatch phase, and the static kernel is as good) */
   uint32_t last_relay_launches = 0;
   uint64_t last_relay_parks = 0, last_relay_waiters = 0;
-  unsigned relay_resident_blocks[3][2] = {{0, 0}, {0, 0}, {0, 0}}; /* cached occupancy query per kernel instantiation */
+  unsigned relay_resident_blocks[4][3][2] = {}; /* cached occupancy query per kernel instantiation: [log2 supersample][kind][fast] */
   int relay_resident_threads = 0;                                  /* ... valid for this workgroup size */
   int block_threads = 0; /* workgroup size of the static / relay kernels: 64, 128 or 256; 0 = automatic */
   Event ev2;
@@ -99,6 +99,8 @@ struct curvis_ctx {
   int blocks_per_cu = 0;    /* 0 = occupancy query */
   int fast_math = 1;        /* 1 shared-reciprocal step (ray_step_fast), 0 compiler IEEE div/sqrt */
   int fuse_shade = 1;       /* static kernel shades in its epilogue (no ray store, no shade launch) */
+  int supersample = 1;      /* N in {1, 2, 4, 8}: every render call traces N x N rays per pixel of the cameras' resolution and the
+                               kernels' epilogues average them (kernels_geodesic.h resolve_store); frames stay res_x x res_y */
   int sampling_speculation = -1; /* efficient renderer: depth of the speculative subtree evaluated below every
                                     refined interval (0 = one launch per refinement round, no speculation;
                                     -1 = automatic: 10 for one or two frames, 6 for three to five, 4 for larger batches;
@@ -177,6 +179,28 @@ auto with_kind(int kind, F &&f) {
 template <typename F>
 auto with_flag(bool flag, F &&f) {
   return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+/* the supersampling factor (option "supersample": 1, 2, 4 or 8 -- the option's writer admits nothing else) as a type */
+template <typename F>
+auto with_supersample(uint32_t ss, F &&f) {
+  switch (ss) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 1>{});
+  }
+}
+inline unsigned supersample_log2(uint32_t ss) { return ss == 8 ? 3u : ss == 4 ? 2u : ss == 2 ? 1u : 0u; }
+/* the cameras of a supersampled call: the same sensor at ss times the resolution (pixel (ss x, ss y) of it is pixel (x, y) of the
+ * original, cv_device.h ray_init); false when a resolution no longer fits 32 bits */
+inline bool supersampled_cameras(const curvis_camera *cams, uint32_t n_frames, uint32_t ss, std::vector<curvis_camera> &out) {
+  out.assign(cams, cams + n_frames);
+  for (curvis_camera &c : out) {
+    if ((uint64_t)c.res_x * ss > 0xFFFFFFFFull || (uint64_t)c.res_y * ss > 0xFFFFFFFFull) return false;
+    c.res_x *= ss;
+    c.res_y *= ss;
+  }
+  return true;
 }
 
 /* ---- overlapped download of the frames (option "async_download" = 1) -------------------------------------------------
@@ -338,8 +362,9 @@ unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
 }
 
 /* grid = fresh workgroups + relay workgroups; see geodesic_relay */
-template <int KIND, bool FAST>
+template <int KIND, bool FAST, int SS>
 int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
+  void (*const kernel)(const IntegrateParams, const RelayArgs) = geodesic_relay<KIND, FAST, SS>;
   const size_t bytes = sizeof(RelayQueue) + sizeof(unsigned) * kRelayRing;
   if (int rc = ctx->d_rq.reserve(ctx, bytes)) return rc;
   RelayArgs A;
@@ -363,13 +388,13 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
   A.corrupt_ticket = ctx->relay_test_corrupt ? 1u : 0u;
   ctx->relay_test_corrupt = 0;
   if (ctx->relay_resident_threads != (int)bt) {
-    for (auto &row : ctx->relay_resident_blocks) row[0] = row[1] = 0;
+    std::memset(ctx->relay_resident_blocks, 0, sizeof ctx->relay_resident_blocks);
     ctx->relay_resident_threads = (int)bt;
   }
-  unsigned &cached = ctx->relay_resident_blocks[KIND][FAST ? 1 : 0];
+  unsigned &cached = ctx->relay_resident_blocks[supersample_log2(SS)][KIND][FAST ? 1 : 0];
   if (cached == 0) {
     int per_cu = 0;
-    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, geodesic_relay<KIND, FAST>, (int)bt, 0));
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)bt, 0));
     if (per_cu <= 0) per_cu = 1;
     cached = (unsigned)per_cu * (unsigned)ctx->prop.multiProcessorCount;
   }
@@ -380,15 +405,25 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
    * workgroups leave at once */
   unsigned long long relay_blocks = resident_blocks * 24ull;
   if (relay_blocks > fresh_blocks * 2ull + resident_blocks) relay_blocks = fresh_blocks * 2ull + resident_blocks;
-  hipLaunchKernelGGL((geodesic_relay<KIND, FAST>), dim3((unsigned)(fresh_blocks + relay_blocks)), dim3(bt), 0, ctx->stream,
-                     P, A);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(fresh_blocks + relay_blocks)), dim3(bt), 0, ctx->stream, P, A);
+  HIP_TRY(ctx, hipGetLastError());
+  return CURVIS_OK;
+}
+
+/* a supersampled launch (render_impl admits it on the fused paths only): the relay kernel, or the static one */
+template <int KIND, bool FAST, int SS>
+int launch_integrate_ss(curvis_ctx *ctx, const IntegrateParams &P, int relay) {
+  if (relay) return launch_relay<KIND, FAST, SS>(ctx, P, relay == 2);
+  const unsigned bt = integrate_block_threads(ctx, KIND);
+  const unsigned long long blocks = (P.total_rays + bt - 1ull) / bt;
+  hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS>), dim3((unsigned)blocks), dim3(bt), 0, ctx->stream, P);
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
 
 template <int KIND, bool PHI, bool FAST>
 int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int relay) {
-  if (relay && fused) return launch_relay<KIND, FAST>(ctx, P, relay == 2);
+  if (relay && fused) return launch_relay<KIND, FAST, 1>(ctx, P, relay == 2);
   if (ctx->variant != 0) {
     const unsigned bt = integrate_block_threads(ctx, KIND);
     const unsigned long long blocks = (P.total_rays + bt - 1ull) / bt;
@@ -414,9 +449,17 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int 
 
 
 /* phi is integrated for the debug dump only, which is never fused and never relayed */
-int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P) {
+int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P, uint32_t ss) {
   return with_kind(kind, [&](auto K) {
     constexpr int KIND = decltype(K)::value;
+    if (ss > 1)
+      return with_flag(fast, [&](auto F) {
+        return with_supersample(ss, [&](auto N) {
+          constexpr int SS = decltype(N)::value;
+          if constexpr (SS > 1) return launch_integrate_ss<KIND, decltype(F)::value, SS>(ctx, P, relay);
+          else return (int)CURVIS_E_INVALID;
+        });
+      });
     if (phi) return with_flag(fast, [&](auto F) { return launch_integrate<KIND, true, decltype(F)::value>(ctx, P, false, 0); });
     return with_flag(fast, [&](auto F) { return launch_integrate<KIND, false, decltype(F)::value>(ctx, P, fused, relay); });
   });
@@ -460,16 +503,18 @@ struct BruteCall {
   curvis_ray_debug *dbg_out;
   curvis_stats *stats;
   uint32_t row_begin, row_count; /* row band (curvis_render_brute_rows); row_count = 0: the whole frame */
+  uint32_t ss;                   /* supersampling factor.  With ss > 1 the cameras, the band, W and H are those of the ss times finer
+                                    RAY grid (what the kernels run over); npix and fb_bytes are always those of the frames written */
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
   size_t npix = 0, fb_bytes = 0;
 };
-int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
+int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin,
-                uint32_t row_count);
+                uint32_t row_count, uint32_t ss);
 /* the same frames once more (the relay kernel's fall-backs and its checker): with the caller's outputs, or into d_fb only */
 int render_again(curvis_ctx *ctx, const BruteCall &c, bool deliver) {
-  return render_impl(ctx, c.metric, c.cams, c.n_frames, c.max_iter, c.max_radius, c.delta, deliver ? c.rgb_out : nullptr,
-                     deliver ? c.dbg_out : nullptr, deliver ? c.stats : nullptr, c.row_begin, c.row_count);
+  return render_rays(ctx, c.metric, c.cams, c.n_frames, c.max_iter, c.max_radius, c.delta, deliver ? c.rgb_out : nullptr,
+                     deliver ? c.dbg_out : nullptr, deliver ? c.stats : nullptr, c.row_begin, c.row_count, c.ss);
 }
 /* a piece's answer when the relay kernel has just been switched off for this context (waves that gave up, a checked launch that
  * differs): render_impl renders the call again -- the static kernel takes it */
@@ -567,7 +612,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   Q.counters = FC;
 
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P);
+  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P, c.ss);
   if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   if (trace) {
@@ -613,7 +658,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
     if (hq->finished >= n_tiles) break;
     if (ctx->last_relay_launches++ > 64)
       return fail(ctx, CURVIS_E_HIP, "relay kernel: tiles still unfinished after 64 relay launches");
-    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P);
+    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P, c.ss);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
@@ -671,9 +716,9 @@ struct LastRenderStats {
  * reports it on stderr, counts it ("relay_mismatches"), switches the context to the static kernel and asks for the call to be
  * rendered again (kRenderAgain): the caller gets the static kernel's frame.  Called after a relay render, d_fb holding its frames. */
 int relay_seat_belt(curvis_ctx *ctx, const BruteCall &c) {
-  /* everything that shapes the hand-over pattern: frame size and count, metric and step flavour, the band, the step cap, the
-   * segment length and hop limit in force */
-  const std::array<uint32_t, 9> shape = {c.W, c.H, c.n_frames, (uint32_t)c.metric->kind, (uint32_t)(ctx->fast_math != 0 ? 1 : 0),
+  /* everything that shapes the hand-over pattern: size of the ray grid and frame count, metric, step flavour and supersampling
+   * factor (another epilogue), the band, the step cap, the segment length and hop limit in force */
+  const std::array<uint32_t, 9> shape = {c.W, c.H, c.n_frames, (uint32_t)c.metric->kind, (uint32_t)(ctx->fast_math != 0 ? 1 : 0) | (c.ss << 8),
                                          c.row_begin, c.row_count, c.max_iter,
                                          (uint32_t)ctx->relay_segment * 256u + (uint32_t)std::max(0, ctx->relay_max_hops)};
   bool auto_check = false;
@@ -749,15 +794,16 @@ void replay_debug_time(const BruteCall &c) {
   }
 }
 
-int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames,
+/* cameras, band and `ss` as BruteCall has them: in units of the ray grid */
+int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames,
                 uint32_t max_iterations, double max_radius, double delta, uint8_t *rgb_out,
-                curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0, uint32_t row_count = 0) {
+                curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin, uint32_t row_count, uint32_t ss) {
   if (!ctx) return CURVIS_E_INVALID;
   if (!metric || !cams || n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   const auto t_begin = std::chrono::steady_clock::now();
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
-  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count};
+  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, ss};
   const uint32_t H_full = cams[0].res_y;
   c.W = cams[0].res_x;
   if (c.W == 0 || H_full == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
@@ -777,7 +823,7 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
   if (!ctx->sky[0].texels || !ctx->sky[1].texels) return fail(ctx, CURVIS_E_NO_SKY, "both background images must be set");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-  c.npix = (size_t)c.W * c.H;
+  c.npix = (size_t)(c.W / ss) * (c.H / ss);
   c.fb_bytes = c.npix * 3 * n_frames;
   if ((rc = fb_begin_write(ctx, c.fb_bytes))) return rc;
   ctx->fb_bytes = c.fb_bytes;
@@ -820,6 +866,27 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
     stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   return CURVIS_OK;
+}
+
+/* the brute renderer's entry points, in the caller's units.  Option "supersample" = N > 1: the same call over the N times finer ray
+ * grid -- cameras of N res_x x N res_y, the band in fine rows -- whose fused epilogues write res_x x res_y frames; every counter is
+ * that of the fine render.  Call shapes without a tile-local resolve are refused. */
+int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
+                double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
+                uint32_t row_count = 0) {
+  const uint32_t ss = ctx ? (uint32_t)ctx->supersample : 1u;
+  if (ss <= 1u || !metric || !cams || n_frames == 0)
+    return render_rays(ctx, metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u);
+  if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)");
+  if (ctx->variant == 0)
+    return fail(ctx, CURVIS_E_INVALID, "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve");
+  if (ctx->fuse_shade == 0)
+    return fail(ctx, CURVIS_E_INVALID, "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve");
+  std::vector<curvis_camera> fine;
+  if (!supersampled_cameras(cams, n_frames, ss, fine) || (uint64_t)row_begin * ss > 0xFFFFFFFFull || (uint64_t)row_count * ss > 0xFFFFFFFFull)
+    return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
+  return render_rays(ctx, metric, fine.data(), n_frames, max_iterations, max_radius, delta, rgb_out, nullptr, stats, row_begin * ss,
+                     row_count * ss, ss);
 }
 
 }  // namespace

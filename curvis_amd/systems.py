@@ -718,8 +718,33 @@ def compute_photon_trajectory(photon, metric, iterations, delta, context=None):
     return states[:-1]
 
 
+def check_supersample(supersample):
+    """the supersampling factor as an int, or ValueError: 1, 2, 4 or 8 rays per pixel and axis (library option "supersample")"""
+    if isinstance(supersample, bool) or not isinstance(supersample, (int, np.integer)) or int(supersample) not in (1, 2, 4, 8):
+        raise ValueError("supersample must be 1, 2, 4 or 8")
+    return int(supersample)
+
+
+class _Supersampled:
+    """the context's "supersample" option set to `factor` for the duration of a render call, then put back"""
+
+    def __init__(self, context, factor):
+        self.context, self.factor = context, factor
+
+    def __enter__(self):
+        self.before = self.context.get_option("supersample")
+        if self.before != self.factor:
+            self.context.set_option("supersample", self.factor)
+
+    def __exit__(self, *exc):
+        if self.before != self.factor:
+            self.context.set_option("supersample", self.before)
+        return False
+
+
 class RelativisticSystem:
-    """RelativisticSystem<M> (src/systems.rs:68-73)."""
+    """RelativisticSystem<M> (src/systems.rs:68-73).  The three renderers take supersample=N (1, 2, 4 or 8; not in the
+    reference): N x N rays per pixel, averaged on the device into the camera's resolution."""
 
     def __init__(self, metric, background_positive, background_negative, camera, context=None):
         self.metric = metric
@@ -736,29 +761,35 @@ class RelativisticSystem:
         if ctx._sky_objs[1] is not self.background_negative:
             ctx.set_sky(1, self.background_negative)
 
-    def render_image(self, max_iterations, max_radius, delta):
+    def render_image(self, max_iterations, max_radius, delta, supersample=1):
         """The per-pixel renderer; returns an HxWx3 uint8 array (DynamicImage::ImageRgb8)."""
+        factor = check_supersample(supersample)
         self._bind_skies()
-        rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
+        with _Supersampled(self.context, factor):
+            rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
         self.last_stats = st
         return rgb
 
     def render_image_efficient(self, max_iterations_propagation, max_radius, delta, alpha_nums,
                                max_iterations_sampling, sampling_convergence_threshold_1,
-                               sampling_convergence_threshold_2):
+                               sampling_convergence_threshold_2, supersample=1):
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
+        factor = check_supersample(supersample)
         self._bind_skies()
-        rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
-                                                alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
-                                                sampling_convergence_threshold_2)
+        with _Supersampled(self.context, factor):
+            rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
+                                                    alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
+                                                    sampling_convergence_threshold_2)
         self.last_stats = st
         return rgb
 
-    def render_image_direct(self, max_iterations_propagation, max_radius, delta):
+    def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1):
         """NOT in the reference: the image render_image_efficient approximates, with compute_escape_angle evaluated
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
+        factor = check_supersample(supersample)
         self._bind_skies()
-        rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
+        with _Supersampled(self.context, factor):
+            rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
         self.last_stats = st
         return rgb
 

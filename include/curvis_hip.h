@@ -374,6 +374,15 @@ int curvis_ctx_download_wait(curvis_ctx *ctx);
  * "blocks_per_cu", "fast_math"
  * (1 = shared-reciprocal Euler step, 0 = compiler IEEE division/sqrt; identical results), "fuse_shade"
  * (1 = the static kernel shades in its epilogue, 0 = final states staged in HBM + separate shade kernel),
+ * "supersample" (N = 1, 2, 4 or 8, default 1; anything else is refused with CURVIS_E_INVALID and the old value stays.  With N > 1
+ * every render entry point -- brute, rows, batch, efficient, efficient batch, direct -- traces N x N rays per pixel of the cameras'
+ * res_x x res_y and still returns res_x x res_y frames: with A the frame the same renderer gives at supersample = 1 for the same
+ * cameras at N res_x x N res_y, out[y][x][c] = (sum of the 8-bit values A[N y + j][N x + i][c], i, j < N, + N^2 / 2) >> (2 log2 N);
+ * the kernels average inside the wave that holds an 8x8 tile of the fine grid, which is why N divides 8.  Every counter --
+ * curvis_stats, curvis_ctx_frame_stats, the sampler's records -- is that of the fine render, so rays = N^2 res_x res_y, also for
+ * the efficient and direct renderers; a row band is given in output rows.  Framebuffer, downloads and the PNG front end see
+ * res_x x res_y frames.  Refused with CURVIS_E_INVALID while N > 1: curvis_render_brute_debug (one record per ray),
+ * "variant" = 0 and "fuse_shade" = 0 (rays staged one by one: no tile-local resolve)),
  * "max_store_bytes" (ray-store budget that bounds the frames per launch of a batch),
  * "sampling_speculation" (efficient renderer: depth of the speculative dyadic subtree evaluated below every
  * refined interval; 0 = one launch per refinement round; default -1 = automatic, 10 for one or two frames, 6 for three to five and 4

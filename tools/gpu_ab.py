@@ -44,9 +44,10 @@ NAMES = os.environ.get("LIBS", "old,new").split(",")
 res = {n: [] for n in NAMES}
 for rnd in range(int(os.environ.get("ROUNDS", "4"))):
     for name in NAMES:
-        r = subprocess.run([sys.executable, "-c", CHILD, os.path.join(root, "build", "ab", name + ".so")], capture_output=True, text=True)
+        r = subprocess.run([sys.executable, "-c", CHILD, os.path.join(root, "build", "ab", name + ".so")], capture_output=True, text=True, timeout=300)
         vals = [float(v) for v in r.stdout.split()] if r.returncode == 0 else None
         print(name, r.stdout.strip() if vals else r.stderr[-400:], flush=True)
-        if vals: res[name].append(vals)
+        if not vals: sys.exit("child failed (%d): nothing more is started on the GPU" % r.returncode)
+        res[name].append(vals)
 for name in res:
     print(name, "median over rounds [ellis x1, ellis x6 per frame, interstellar x1, efficient-image sampling kernels, efficient pixel kernel per frame of a 32-frame call] ms:", np.median(np.array(res[name]), axis=0))
