@@ -74,6 +74,7 @@ SYMBOLS = {
     "curvis_vector_to_direction": (C.c_int, [C.POINTER(Metric), _dp, _dp, _dp]),
     "curvis_update_relativistic_object": (C.c_int, [C.POINTER(Metric), _dp, _dp, C.c_double]),
     "curvis_sky_texel_index": (C.c_int, [C.c_uint32, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "curvis_sky_bilinear_taps": (C.c_int, [C.c_uint32, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "curvis_render_brute": (C.c_int, [_vp, C.POINTER(Metric), C.POINTER(CameraC), C.c_uint32, C.c_double, C.c_double,
                                       _vp, C.POINTER(Stats)]),
     "curvis_render_brute_rows": (C.c_int, [_vp, C.POINTER(Metric), C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_uint32,
@@ -125,6 +126,7 @@ SYMBOLS = {
     "curvis_selftest_math3": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_size_t]),
     "curvis_selftest_fast_step": (C.c_int, [_vp, C.POINTER(Metric), C.c_double, C.c_double, _dp, C.c_size_t, _dp]),
     "curvis_selftest_sky_indices": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _dp, _dp, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "curvis_selftest_sky_bilinear": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _dp, _vp, _dp, C.c_size_t, C.POINTER(C.c_uint32), _vp]),
 }
 
 _lib = None

@@ -30,6 +30,10 @@
  *   geodesic_static / geodesic_relay / direct_kernel<..., SS>, efficient_pixel_ss_kernel<SS>   option "supersample" = SS in
  *       {2, 4, 8} (SS = 1: the kernels above): the same kernels over the SS times finer ray grid; the wave that holds an 8x8 tile of it averages every SS x SS
  *       block across its lanes (DPP / ds_swizzle / ds_bpermute) and stores one pixel per block (resolve_store).
+ *   the same with a trailing FILTER = 1 (efficient_pixel_kernel<1>, efficient_pixel_ss_kernel<SS, 1>)   option "sky_filter" = 1: the
+ *       epilogues blend the four texels around the direction (cv_device.h sky_bilinear_taps / sky_bilinear_blend) instead of
+ *       fetching the nearest; FILTER = 0 are the kernels above, instruction for instruction.
+ *   selftest_sky_bilinear_kernel           the two functions alone, both instantiations, on the tests' directions.
  *   selftest_math_kernel                   cv_math.h / IEEE div / sqrt / hardware seeds for the tests.
  *   selftest_sky_indices_kernel            cvk::sky_indices (direction -> texel), both instantiations, on the tests' directions.
  *   FAST = shared-reciprocal Euler step (cv_device.h ray_step_fast), !FAST = compiler IEEE div/sqrt;
@@ -542,6 +546,27 @@ int curvis_sky_texel_index(uint32_t w, uint32_t h, const double inv_rot[9], cons
   return (tx >= w || ty >= h) ? CURVIS_E_INVALID : CURVIS_OK;
 }
 
+int curvis_sky_bilinear_taps(uint32_t w, uint32_t h, const double inv_rot[9], const double v[3], uint32_t taps[6], uint32_t raw[2]) {
+  if (!v || !taps || !raw || w == 0 || h == 0) return CURVIS_E_INVALID;
+  cvk::SkyParams S;
+  S.texels = nullptr;
+  S.w = w;
+  S.h = h;
+  for (int i = 0; i < 9; ++i) S.inv_rot[i] = inv_rot ? inv_rot[i] : ((i % 4 == 0) ? 1.0 : 0.0);
+  if (w > kSkyFilterMaxSide || h > kSkyFilterMaxSide) { /* 256 w no longer a u32: the nearest indices, no taps */
+    unsigned tx = 0, ty = 0;
+    cvk::sky_indices(S, v[0], v[1], v[2], tx, ty);
+    raw[0] = tx, raw[1] = ty;
+    for (int i = 0; i < 6; ++i) taps[i] = 0;
+    return CURVIS_E_INVALID;
+  }
+  cvk::SkyTaps t;
+  cvk::sky_bilinear_taps(S, v[0], v[1], v[2], t);
+  taps[0] = t.x0, taps[1] = t.x1, taps[2] = t.y0, taps[3] = t.y1, taps[4] = t.fx, taps[5] = t.fy;
+  raw[0] = t.tx, raw[1] = t.ty;
+  return t.oob ? CURVIS_E_INVALID : CURVIS_OK;
+}
+
 int curvis_render_brute(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *camera,
                         uint32_t max_iterations, double max_radius, double delta, uint8_t *rgb_out,
                         curvis_stats *stats) {
@@ -885,6 +910,12 @@ const OptionEntry kOptions[] = {
        c->supersample = (int)v;
        return CURVIS_OK;
      }},
+    {"sky_filter", OPT_READ(c->sky_filter),
+     [](curvis_ctx *c, int64_t v) -> int {
+       if (v != 0 && v != 1) return fail(c, CURVIS_E_INVALID, "sky_filter must be 0 (nearest) or 1 (bilinear)");
+       c->sky_filter = (int)v;
+       return CURVIS_OK;
+     }},
     OPT_RW(device_sampler, int),
     {"device_sampler_min_frames", OPT_READ(c->device_sampler_min_frames),
      [](curvis_ctx *c, int64_t v) -> int {
@@ -1027,6 +1058,38 @@ int curvis_selftest_sky_indices(curvis_ctx *ctx, uint32_t w, uint32_t h, const d
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipMemcpy(out, dout, n * 4 * sizeof(unsigned), hipMemcpyDeviceToHost));
+  return CURVIS_OK;
+}
+
+int curvis_selftest_sky_bilinear(curvis_ctx *ctx, uint32_t w, uint32_t h, const double inv_rot[9], const uint8_t *rgba, const double *dirs,
+                                 size_t n, uint32_t *out_taps, uint8_t *out_rgb) {
+  if (!ctx || !inv_rot || !rgba || !dirs || !out_taps || !out_rgb || w == 0 || h == 0) return CURVIS_E_INVALID;
+  if (w > kSkyFilterMaxSide || h > kSkyFilterMaxSide) return fail(ctx, CURVIS_E_INVALID, "sky_filter: a sky of more than 2^23 texels per side");
+  if (n == 0) return CURVIS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const curvis_ctx::PixRecips &cached = ctx->pix_recips;
+  cvk::PixelRecips R; /* as curvis_selftest_sky_indices */
+  if (int rc = ensure_pixel_recips(ctx, cached.valid ? cached.res_x : 1.0, cached.valid ? cached.res_y : 1.0, R)) return rc;
+  DeviceBuffer<double> din;
+  DeviceBuffer<unsigned> dsky, dtaps;
+  DeviceBuffer<unsigned char> drgb;
+  const size_t texels = (size_t)w * h;
+  if (int rc = dsky.reserve(ctx, texels)) return rc;
+  if (int rc = din.reserve(ctx, n * 3)) return rc;
+  if (int rc = dtaps.reserve(ctx, n * 12)) return rc;
+  if (int rc = drgb.reserve(ctx, n * 6)) return rc;
+  HIP_TRY(ctx, hipMemcpy(dsky, rgba, texels * 4, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(din, dirs, n * 3 * sizeof(double), hipMemcpyHostToDevice));
+  cvk::SkyParams S;
+  S.texels = dsky.p;
+  S.w = w;
+  S.h = h;
+  for (int i = 0; i < 9; ++i) S.inv_rot[i] = inv_rot[i];
+  hipLaunchKernelGGL(selftest_sky_bilinear_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, S, R, din.p, n, dtaps.p, drgb.p);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out_taps, dtaps, n * 12 * sizeof(unsigned), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(out_rgb, drgb, n * 6, hipMemcpyDeviceToHost));
   return CURVIS_OK;
 }
 

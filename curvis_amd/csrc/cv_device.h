@@ -624,6 +624,48 @@ CV_HD void sky_indices(const SkyParams &S, double d0, double d1, double d2, unsi
   tx = rust_as_u32(rem_euclid_pos(0.5 - div_angle<SHARED>(phi, TWO_PI, y_two_pi), 1.0) * (double)S.w);
 }
 
+/* ---- option "sky_filter" = 1: bilinear lookup (include/curvis_hip.h has the definition; the numbers below are its steps).
+ * The four texels a ray blends and their 8-bit weights, from the indices sky_indices returns on the virtual sky of 256 w x 256 h
+ * texels: scaling by 2^8 commutes with every rounding, so X >> 8, Y >> 8 are sky_indices' raw tx, ty bit for bit and the filter costs
+ * no FP64 operation of its own.  Needs w, h <= 2^23 (checked on the host: 256 w must stay a u32). */
+struct SkyTaps {
+  unsigned x0, x1, y0, y1; /* columns and rows of the four texels, all inside the sky */
+  unsigned fx, fy;         /* weights of x1 and y1, 0..255 (those of x0 and y0: 256 - fx, 256 - fy) */
+  unsigned tx, ty;         /* X >> 8, Y >> 8: the nearest lookup's raw indices */
+  bool oob;                /* tx >= w or ty >= h: the rays the nearest lookup counts in n_oob */
+};
+template <bool SHARED = false>
+CV_HD void sky_bilinear_taps(const SkyParams &S, double d0, double d1, double d2, SkyTaps &t, double y_pi = 0.0, double y_two_pi = 0.0) {
+  const unsigned fine_w = S.w << 8, fine_h = S.h << 8;
+  SkyParams F = S; /* 1: the same lookup, the same orientation, 256 times the size; texels are not read */
+  F.w = fine_w;
+  F.h = fine_h;
+  unsigned X, Y;
+  sky_indices<SHARED>(F, d0, d1, d2, X, Y, y_pi, y_two_pi);
+  t.tx = X >> 8; /* 2 */
+  t.ty = Y >> 8;
+  t.oob = t.tx >= S.w || t.ty >= S.h;
+  const unsigned Xc = X < fine_w - 1u ? X : fine_w - 1u, Yc = Y < fine_h - 1u ? Y : fine_h - 1u;
+  const unsigned U = Xc >= 128u ? Xc - 128u : Xc + fine_w - 128u; /* 3: texel centres at 256 x + 128; longitude wraps */
+  t.x0 = U >> 8;
+  t.fx = U & 255u;
+  t.x1 = t.x0 + 1u == S.w ? 0u : t.x0 + 1u;
+  const unsigned V = Yc >= 128u ? Yc - 128u : 0u; /* 4: colatitude clamps */
+  t.y0 = V >> 8;
+  t.fy = V & 255u;
+  t.y1 = t.y0 + 1u < S.h ? t.y0 + 1u : S.h - 1u;
+}
+/* 5: the blend of four packed RGBA8 texels -- t00 = T[y0][x0], t01 = T[y0][x1], t10 = T[y1][x0], t11 = T[y1][x1] -- per colour channel
+ * (w00 c00 + w01 c01 + w10 c10 + w11 c11 + 32768) >> 16 with integer weights that sum to 65536: at most 255 * 65536 + 32768 < 2^32,
+ * one rounding, half up.  Alpha is ignored (as put_pixel ignores it) and comes back as 255. */
+CV_HD unsigned sky_bilinear_blend(unsigned t00, unsigned t01, unsigned t10, unsigned t11, unsigned fx, unsigned fy) {
+  const unsigned w11 = fx * fy, w01 = fx * (256u - fy), w10 = (256u - fx) * fy, w00 = (256u - fx) * (256u - fy);
+  const unsigned r = w00 * (t00 & 255u) + w01 * (t01 & 255u) + w10 * (t10 & 255u) + w11 * (t11 & 255u);
+  const unsigned g = w00 * ((t00 >> 8) & 255u) + w01 * ((t01 >> 8) & 255u) + w10 * ((t10 >> 8) & 255u) + w11 * ((t11 >> 8) & 255u);
+  const unsigned b = w00 * ((t00 >> 16) & 255u) + w01 * ((t01 >> 16) & 255u) + w10 * ((t10 >> 16) & 255u) + w11 * ((t11 >> 16) & 255u);
+  return 0xFF000000u | ((r + 32768u) >> 16) | (((g + 32768u) >> 16) << 8) | (((b + 32768u) >> 16) << 16);
+}
+
 }  // namespace cvk
 
 #endif /* CURVIS_CV_DEVICE_H */

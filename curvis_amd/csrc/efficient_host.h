@@ -15,6 +15,7 @@ struct EfficientCall {
   double max_radius, delta;
   uint32_t alpha_nums, max_iterations_sampling;
   double thr1, thr2;
+  uint32_t filter = 0; /* option "sky_filter" for this call */
   uint32_t ss = 1; /* supersampling factor: with ss > 1 `cams` are those of the ss times finer pixel grid (render_efficient_impl) */
 };
 
@@ -142,18 +143,23 @@ int make_pixel_params(curvis_ctx *ctx, uint32_t n_frames, uint32_t W, uint32_t H
 }
 
 /* K3 over n_frames frames of Q.W x Q.H pixels: linear pixel order, or -- supersampled -- 8x8 tiles of the fine grid, four per workgroup */
-int launch_pixel_kernel(curvis_ctx *ctx, const EfficientPixelParams &Q, uint32_t n_frames, uint32_t ss) {
+int launch_pixel_kernel(curvis_ctx *ctx, const EfficientPixelParams &Q, uint32_t n_frames, uint32_t ss, uint32_t filter) {
   if (ss > 1u) {
     const unsigned long long tiles = (unsigned long long)((Q.W + 7u) / 8u) * ((Q.H + 7u) / 8u);
     if ((tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
     with_supersample(ss, [&](auto N) {
-      constexpr int SS = decltype(N)::value;
-      if constexpr (SS > 1)
-        hipLaunchKernelGGL(efficient_pixel_ss_kernel<SS>, dim3((unsigned)((tiles + 3ull) / 4ull), n_frames), dim3(256), 0, ctx->stream, Q);
+      with_filter(filter, [&](auto L) {
+        constexpr int SS = decltype(N)::value, FILTER = decltype(L)::value;
+        if constexpr (SS > 1)
+          hipLaunchKernelGGL((efficient_pixel_ss_kernel<SS, FILTER>), dim3((unsigned)((tiles + 3ull) / 4ull), n_frames), dim3(256), 0,
+                             ctx->stream, Q);
+      });
     });
   } else {
     const size_t npix = (size_t)Q.W * Q.H;
-    hipLaunchKernelGGL(efficient_pixel_kernel, dim3((unsigned)((npix + 255) / 256), n_frames), dim3(256), 0, ctx->stream, Q);
+    with_filter(filter, [&](auto L) {
+      hipLaunchKernelGGL(efficient_pixel_kernel<decltype(L)::value>, dim3((unsigned)((npix + 255) / 256), n_frames), dim3(256), 0, ctx->stream, Q);
+    });
   }
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
@@ -468,7 +474,7 @@ int render_efficient_device(curvis_ctx *ctx, const EfficientCall &c, const cvk::
   const PixelInputs in = {ctx->d_eff, o_cams, o_fr, S.d, S.o_tab_off, S.o_tab_n, S.o_grid_off, S.o_grid, S.o_tab[0], S.o_tab[3],
                           S.o_tab[4], S.o_tab[5], S.o_tab[6]};
   if ((rc = make_pixel_params(ctx, n_frames, W, H, FC, in, Q))) return rc;
-  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss))) return rc;
+  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss, c.filter))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words, hipMemcpyDeviceToHost, ctx->stream));
   const auto t_launched = std::chrono::steady_clock::now();
@@ -833,7 +839,7 @@ int render_pixels_staged(curvis_ctx *ctx, const EfficientCall &c, const std::vec
   const PixelInputs in = {ctx->d_eff, o_cams, o_fr, ctx->d_eff, o_to, o_tn, o_go, o_gr, o_sx, o_me, o_ce, o_ms, o_cs};
   if ((rc = make_pixel_params(ctx, n_frames, W, H, FC, in, Q))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss))) return rc;
+  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss, c.filter))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words,
                               hipMemcpyDeviceToHost, ctx->stream));
@@ -855,6 +861,10 @@ int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *r
   /* option "supersample" = N > 1: the call over the N times finer pixel grid (the samplers see camera radii only and do not notice),
    * averaged into res_x x res_y frames by the per-pixel kernel; "rays" are fine pixels */
   EfficientCall c = call;
+  if (ctx->sky_filter) { /* option "sky_filter" = 1: the per-pixel kernel blends; the samplers never see a sky */
+    if (int rc = check_sky_filter_sizes(ctx)) return rc;
+    c.filter = 1u;
+  }
   std::vector<curvis_camera> fine;
   if (ctx->supersample > 1) {
     c.ss = (uint32_t)ctx->supersample;
@@ -937,7 +947,9 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   /* option "supersample" = N > 1: the camera of the N times finer grid, averaged into res_x x res_y by the kernel's epilogue */
-  const uint32_t ss = (uint32_t)ctx->supersample;
+  const uint32_t ss = (uint32_t)ctx->supersample, filter = (uint32_t)ctx->sky_filter;
+  if (filter)
+    if (int rc2 = check_sky_filter_sizes(ctx)) return rc2;
   std::vector<curvis_camera> fine;
   if (ss > 1u) {
     if (!supersampled_cameras(cam, 1, ss, fine)) return fail(ctx, CURVIS_E_INVALID, "frame too large");
@@ -979,10 +991,12 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   with_kind(metric->kind, [&](auto K) {
     with_flag(ctx->fast_math != 0, [&](auto F) {
       with_supersample(ss, [&](auto N) {
-        constexpr int KIND = decltype(K)::value, SS = decltype(N)::value;
-        constexpr bool FAST = decltype(F)::value;
-        const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
-        hipLaunchKernelGGL((direct_kernel<KIND, FAST, SS>), grid, dim3(256), 0, ctx->stream, P);
+        with_filter(filter, [&](auto L) {
+          constexpr int KIND = decltype(K)::value, SS = decltype(N)::value, FILTER = decltype(L)::value;
+          constexpr bool FAST = decltype(F)::value;
+          const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
+          hipLaunchKernelGGL((direct_kernel<KIND, FAST, SS, FILTER>), grid, dim3(256), 0, ctx->stream, P);
+        });
       });
     });
   });

@@ -17,8 +17,10 @@ struct Args {
   int encode_bench = 0; /* video, diagnostics: every rendered frame is encoded this many extra times into a scratch file */
   std::string gpu_png = "auto"; /* video: PNG front end on the device (curvis_ctx_deflate_frames): auto = with the fast writer, on, off */
   int supersample = 1; /* rays per pixel and axis, averaged on the device (library option "supersample"): 1, 2, 4 or 8 */
+  int sky_filter = 0; /* sky lookup (library option "sky_filter"): 0 nearest texel, 1 bilinear */
 };
 int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
+int g_sky_filter = 0;  /* Args::sky_filter, likewise */
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(code);
@@ -32,7 +34,7 @@ void usage() {
       "  common: [-m|--metric-settings <TOML FILE>] [-c|--camera-settings <TOML FILE>] [-s|--simulation-settings <TOML FILE>]\n"
       "  extensions: [--mode efficient|brute|direct] [--device N] [--devices N] [--batch B] [--stats FILE]\n"
       "              [--sky-broadcast rccl|upload] [--writers T] [--resume] [--png-level -1..9] [--gpu-png auto|on|off]\n"
-      "              [--contexts-per-device C] [--supersample 1|2|4|8]\n");
+      "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -80,6 +82,11 @@ Args parse_args(int argc, char **argv) {
       take(val);
       if (val != "1" && val != "2" && val != "4" && val != "8") die("error: --supersample must be 1, 2, 4 or 8", 2);
       a.supersample = g_supersample = std::atoi(val.c_str());
+    }
+    else if (key == "--sky-filter") {
+      take(val);
+      if (val != "nearest" && val != "bilinear") die("error: --sky-filter must be nearest or bilinear", 2);
+      a.sky_filter = g_sky_filter = val == "bilinear" ? 1 : 0;
     }
     else if (key == "-h" || key == "--help") { usage(); std::exit(0); }
     else if (!s.empty() && s[0] == '-') die("error: unexpected argument '" + s + "' found", 2);
@@ -228,6 +235,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
     }
   }
   if (g_supersample != 1) check(curvis_ctx_set_option(ctx, "supersample", g_supersample), ctx, what);
+  if (g_sky_filter != 0) check(curvis_ctx_set_option(ctx, "sky_filter", g_sky_filter), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {

@@ -77,8 +77,8 @@ int image_main(const Args &a) {
   if (!a.stats.empty()) {
     FILE *f = std::fopen(a.stats.c_str(), "w");
     if (f) {
-      std::fprintf(f, "{\"frame\": 0, \"mode\": \"%s\", \"supersample\": %d, \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f}\n",
-                   a.mode.c_str(), a.supersample, (unsigned long long)st.rays, (unsigned long long)st.steps, (unsigned long long)st.n_pos,
+      std::fprintf(f, "{\"frame\": 0, \"mode\": \"%s\", \"supersample\": %d, \"sky_filter\": \"%s\", \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f}\n",
+                   a.mode.c_str(), a.supersample, a.sky_filter ? "bilinear" : "nearest", (unsigned long long)st.rays, (unsigned long long)st.steps, (unsigned long long)st.n_pos,
                    (unsigned long long)st.n_neg, (unsigned long long)st.n_none, (unsigned long long)st.n_oob, st.kernel_ms,
                    st.kernel_ms > 0.0 ? (double)st.steps / st.kernel_ms / 1e3 : 0.0);
       std::fclose(f);

@@ -297,6 +297,7 @@ __global__ void recip_chain_kernel(const double *d, double *y, unsigned n) {
  * `curvis video` in the reference's default mode.  (Walking several groups per workgroup to reduce even less often was worse: the
  * compiler hoists the frame's constants out of the loop into 155 VGPRs -- 3 waves per SIMD instead of 8 --, and as a
  * non-inlined call the body spills.)  The RGB8 bytes of a wave's 64 pixels are transposed through LDS and stored as 48 dwords. */
+template <int FILTER = 0> /* option "sky_filter": 0 nearest texel, 1 bilinear (sky_lookup_bilinear, kernels_geodesic.h) */
 __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPixelParams P) {
   __shared__ __attribute__((aligned(16))) unsigned char s_rgb[256 * 3];
   __shared__ unsigned s_cnt[5];
@@ -324,11 +325,15 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
       if (k == 0 ? pos : neg) {
         const cvk::SkyParams &S = P.sky[k];
         unsigned tx, ty;
-        cvk::sky_indices<true>(S, fin[0], fin[1], fin[2], tx, ty, P.recips.y_pi, P.recips.y_two_pi);
-        if (tx >= S.w || ty >= S.h) oob = true;
-        if (tx >= S.w) tx = S.w - 1;
-        if (ty >= S.h) ty = S.h - 1;
-        texel = S.texels[(size_t)ty * S.w + tx];
+        if constexpr (FILTER != 0) { /* the sky's size, pointer and rotation stay scalar operands: the taps' integer work is per lane */
+          if (sky_lookup_bilinear<true>(S, fin[0], fin[1], fin[2], tx, ty, texel, P.recips.y_pi, P.recips.y_two_pi)) oob = true;
+        } else {
+          cvk::sky_indices<true>(S, fin[0], fin[1], fin[2], tx, ty, P.recips.y_pi, P.recips.y_two_pi);
+          if (tx >= S.w || ty >= S.h) oob = true;
+          if (tx >= S.w) tx = S.w - 1;
+          if (ty >= S.h) ty = S.h - 1;
+          texel = S.texels[(size_t)ty * S.w + tx];
+        }
       }
     }
   }
@@ -376,7 +381,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
  * instead of linearly, so that the wave holding a tile averages its SS x SS blocks into the W/SS x H/SS frame (resolve_store,
  * kernels_geodesic.h).  Per fine pixel it is efficient_pixel_kernel: the same interpolation, the same wave-level sky branches, the
  * same per-workgroup statistics (counted in fine pixels). */
-template <int SS>
+template <int SS, int FILTER = 0>
 __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const EfficientPixelParams P) {
   __shared__ unsigned s_cnt[5];
   const unsigned f = blockIdx.y;
@@ -402,11 +407,15 @@ __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const Efficient
       if (k == 0 ? pos : neg) {
         const cvk::SkyParams &S = P.sky[k];
         unsigned tx, ty;
-        cvk::sky_indices<true>(S, fin[0], fin[1], fin[2], tx, ty, P.recips.y_pi, P.recips.y_two_pi);
-        if (tx >= S.w || ty >= S.h) oob = true;
-        if (tx >= S.w) tx = S.w - 1;
-        if (ty >= S.h) ty = S.h - 1;
-        texel = S.texels[(size_t)ty * S.w + tx];
+        if constexpr (FILTER != 0) { /* the sky's size, pointer and rotation stay scalar operands: the taps' integer work is per lane */
+          if (sky_lookup_bilinear<true>(S, fin[0], fin[1], fin[2], tx, ty, texel, P.recips.y_pi, P.recips.y_two_pi)) oob = true;
+        } else {
+          cvk::sky_indices<true>(S, fin[0], fin[1], fin[2], tx, ty, P.recips.y_pi, P.recips.y_two_pi);
+          if (tx >= S.w || ty >= S.h) oob = true;
+          if (tx >= S.w) tx = S.w - 1;
+          if (ty >= S.h) ty = S.h - 1;
+          texel = S.texels[(size_t)ty * S.w + tx];
+        }
       }
     }
   }
@@ -453,7 +462,7 @@ struct DirectParams {
 };
 
 /* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
-template <int KIND, bool FAST, int SS = 1>
+template <int KIND, bool FAST, int SS = 1, int FILTER = 0> /* FILTER: option "sky_filter" */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 4 : 6)))
 void direct_kernel(const DirectParams P) {
   [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */
@@ -494,11 +503,15 @@ void direct_kernel(const DirectParams P) {
       cvk::efficient_final_direction(P.frame, axis, angle, fin);
       const cvk::SkyParams &S = P.sky[code == cvk::CODE_POS ? 0 : 1];
       unsigned tx, ty;
-      cvk::sky_indices(S, fin[0], fin[1], fin[2], tx, ty);
-      if (tx >= S.w || ty >= S.h) oob = 1;
-      if (tx >= S.w) tx = S.w - 1;
-      if (ty >= S.h) ty = S.h - 1;
-      texel = S.texels[(size_t)ty * S.w + tx];
+      if constexpr (FILTER != 0) {
+        if (sky_lookup_bilinear<false>(S, fin[0], fin[1], fin[2], tx, ty, texel)) oob = 1;
+      } else {
+        cvk::sky_indices(S, fin[0], fin[1], fin[2], tx, ty);
+        if (tx >= S.w || ty >= S.h) oob = 1;
+        if (tx >= S.w) tx = S.w - 1;
+        if (ty >= S.h) ty = S.h - 1;
+        texel = S.texels[(size_t)ty * S.w + tx];
+      }
       pos = (code == cvk::CODE_POS);
       neg = (code == cvk::CODE_NEG);
     } else {
@@ -678,6 +691,27 @@ __global__ void selftest_sky_indices_kernel(cvk::SkyParams S, cvk::PixelRecips R
   cvk::sky_indices<true>(S, d0, d1, d2, tx, ty, R.y_pi, R.y_two_pi);
   out[4 * i + 2] = tx;
   out[4 * i + 3] = ty;
+}
+
+/* cvk::sky_bilinear_taps and sky_bilinear_blend on chosen directions (tests/test_gpu_sky_filter.py): S.texels is a w x h sky on the
+ * device; taps = n x 2 x {x0, x1, y0, y1, fx, fy}, rgb = n x 2 x {r, g, b} -- first the plain instantiation (the brute and direct
+ * renderers'), then the one with the call's shared reciprocals (the efficient pixel kernel's) */
+template <bool SHARED>
+__device__ void selftest_sky_bilinear_one(const cvk::SkyParams &S, const cvk::PixelRecips &R, double d0, double d1, double d2, unsigned *o,
+                                          unsigned char *q) {
+  cvk::SkyTaps t;
+  cvk::sky_bilinear_taps<SHARED>(S, d0, d1, d2, t, R.y_pi, R.y_two_pi);
+  o[0] = t.x0, o[1] = t.x1, o[2] = t.y0, o[3] = t.y1, o[4] = t.fx, o[5] = t.fy;
+  const unsigned *row0 = S.texels + (size_t)t.y0 * S.w, *row1 = S.texels + (size_t)t.y1 * S.w;
+  const unsigned c = cvk::sky_bilinear_blend(row0[t.x0], row0[t.x1], row1[t.x0], row1[t.x1], t.fx, t.fy);
+  q[0] = (unsigned char)(c & 0xFF), q[1] = (unsigned char)((c >> 8) & 0xFF), q[2] = (unsigned char)((c >> 16) & 0xFF);
+}
+__global__ void selftest_sky_bilinear_kernel(cvk::SkyParams S, cvk::PixelRecips R, const double *d, size_t n, unsigned *taps, unsigned char *rgb) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double d0 = d[3 * i], d1 = d[3 * i + 1], d2 = d[3 * i + 2];
+  selftest_sky_bilinear_one<false>(S, R, d0, d1, d2, taps + 12 * i, rgb + 6 * i);
+  selftest_sky_bilinear_one<true>(S, R, d0, d1, d2, taps + 12 * i + 6, rgb + 6 * i + 3);
 }
 
 /* One fast Euler step per input state with every quotient of the step recorded (cvk::NoProbe's counterpart): for

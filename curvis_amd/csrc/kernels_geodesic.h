@@ -232,8 +232,24 @@ __device__ __forceinline__ void one_step(const cvk::MetricParams &M, double delt
     cvk::ray_step<KIND, PHI, MathTablesLds<KIND>::WIDE_SC>(M, q, delta);
 }
 
-/* final photon -> tangent direction -> nearest sky texel (rows R9-R10 of SURVEY.md 8a) */
-template <int KIND>
+/* option "sky_filter" = 1: the blend of the four texels around the direction instead of the nearest one (cv_device.h
+ * sky_bilinear_taps / sky_bilinear_blend).  The four gathers are independent of each other: all are issued before the blend
+ * waits for the first.  tx, ty and the return value (out of bounds) are those of the nearest lookup. */
+template <bool SHARED>
+__device__ __forceinline__ bool sky_lookup_bilinear(const cvk::SkyParams &S, double d0, double d1, double d2, unsigned &tx, unsigned &ty,
+                                                    unsigned &texel, double y_pi = 0.0, double y_two_pi = 0.0) {
+  cvk::SkyTaps t;
+  cvk::sky_bilinear_taps<SHARED>(S, d0, d1, d2, t, y_pi, y_two_pi);
+  const unsigned *row0 = S.texels + (size_t)t.y0 * S.w, *row1 = S.texels + (size_t)t.y1 * S.w;
+  const unsigned t00 = row0[t.x0], t01 = row0[t.x1], t10 = row1[t.x0], t11 = row1[t.x1];
+  texel = cvk::sky_bilinear_blend(t00, t01, t10, t11, t.fx, t.fy);
+  tx = t.tx;
+  ty = t.ty;
+  return t.oob;
+}
+
+/* final photon -> tangent direction -> nearest sky texel (rows R9-R10 of SURVEY.md 8a); FILTER: the bilinear blend instead */
+template <int KIND, int FILTER = 0>
 __device__ __forceinline__ unsigned shade_ray(const cvk::MetricParams &M, const cvk::SkyParams *sky, const cvk::Ray &q,
                                               int code, unsigned &tx, unsigned &ty, unsigned &oob) {
   unsigned texel = 0xFF000000u; /* Rgba([0,0,0,255]) */
@@ -242,6 +258,10 @@ __device__ __forceinline__ unsigned shade_ray(const cvk::MetricParams &M, const 
     double d0, d1, d2;
     cvk::ray_direction<KIND>(M, q, d0, d1, d2);
     const cvk::SkyParams &S = sky[code == cvk::CODE_POS ? 0 : 1];
+    if constexpr (FILTER != 0) {
+      if (sky_lookup_bilinear<false>(S, d0, d1, d2, tx, ty, texel)) oob = 1;
+      return texel;
+    }
     cvk::sky_indices(S, d0, d1, d2, tx, ty);
     unsigned cx = tx, cy = ty;
     if (cx >= S.w || cy >= S.h) oob = 1; /* reference: image::get_pixel panics; defined here: clamp + count */
@@ -379,10 +399,11 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
  * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame.
  * SS: supersampling factor (1: one ray per output pixel; 2, 4, 8: P is in units of the fine grid and the epilogue averages,
  * resolve_store above; FUSED only). */
-template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1>
+template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0> /* FILTER: option "sky_filter" (FUSED only) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
 void geodesic_static(const IntegrateParams P) {
   static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");
+  static_assert(FILTER == 0 || (FUSED && !PHI), "the filtered lookup exists in the fused epilogues only");
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -438,7 +459,7 @@ void geodesic_static(const IntegrateParams P) {
     if (valid) {
       if (FUSED) {
         unsigned tx, ty;
-        const unsigned texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
+        const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
         unsigned char *dst = P.fb + slot * 3;
         dst[0] = (unsigned char)(texel & 0xFF);
         dst[1] = (unsigned char)((texel >> 8) & 0xFF);
@@ -454,7 +475,7 @@ void geodesic_static(const IntegrateParams P) {
     unsigned texel = 0u;
     if (valid) {
       unsigned tx, ty;
-      texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
+      texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
       pos = (code == cvk::CODE_POS);
       neg = (code == cvk::CODE_NEG);
       none = (code == cvk::CODE_NONE);
@@ -532,7 +553,7 @@ __device__ __forceinline__ T ld_sys(const T *p) { return __hip_atomic_load(const
 
 /* register budget: the Interstellar instantiation must stay at 5 waves per SIMD (<= 96 VGPRs; its LDS tables allow
  * no more anyway): left alone the allocator takes 97 and drops to four (+6 % time) */
-template <int KIND, bool FAST, int SS = 1> /* SS: supersampling factor, as in geodesic_static */
+template <int KIND, bool FAST, int SS = 1, int FILTER = 0> /* SS: supersampling factor, FILTER: option "sky_filter", as in geodesic_static */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
 void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
   __shared__ MathTablesLds<KIND> s_tab;
@@ -686,7 +707,7 @@ void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
       unsigned frame2, px2, py2;
       if (id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2)) {
         unsigned tx, ty;
-        const unsigned texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
+        const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
         unsigned char *dst = P.fb + ((size_t)frame2 * P.W * P.H + (size_t)py2 * P.W + px2) * 3;
         dst[0] = (unsigned char)(texel & 0xFF);
         dst[1] = (unsigned char)((texel >> 8) & 0xFF);
@@ -700,7 +721,7 @@ void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
       const bool valid2 = id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2);
       if (valid2) {
         unsigned tx, ty;
-        texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
+        texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
         pos = (code == cvk::CODE_POS);
         neg = (code == cvk::CODE_NEG);
         none = (code == cvk::CODE_NONE);

@@ -75,7 +75,7 @@ struct curvis_ctx {
                                        once, there is no dispatch phase, and the static kernel is as good) */
   uint32_t last_relay_launches = 0;
   uint64_t last_relay_parks = 0, last_relay_waiters = 0;
-  unsigned relay_resident_blocks[4][3][2] = {}; /* cached occupancy query per kernel instantiation: [log2 supersample][kind][fast] */
+  unsigned relay_resident_blocks[2][4][3][2] = {}; /* cached occupancy query per kernel instantiation: [sky_filter][log2 supersample][kind][fast] */
   int relay_resident_threads = 0;                                  /* ... valid for this workgroup size */
   int block_threads = 0; /* workgroup size of the static / relay kernels: 64, 128 or 256; 0 = automatic */
   Event ev2;
@@ -101,6 +101,8 @@ struct curvis_ctx {
   int fuse_shade = 1;       /* static kernel shades in its epilogue (no ray store, no shade launch) */
   int supersample = 1;      /* N in {1, 2, 4, 8}: every render call traces N x N rays per pixel of the cameras' resolution and the
                                kernels' epilogues average them (kernels_geodesic.h resolve_store); frames stay res_x x res_y */
+  int sky_filter = 0;       /* 0: a ray takes the nearest sky texel (the reference); 1: the bilinear blend of the four around its
+                               direction, defined in include/curvis_hip.h (cv_device.h sky_bilinear_taps / sky_bilinear_blend) */
   int sampling_speculation = -1; /* efficient renderer: depth of the speculative subtree evaluated below every
                                     refined interval (0 = one launch per refinement round, no speculation;
                                     -1 = automatic: 10 for one or two frames, 6 for three to five, 4 for larger batches;
@@ -189,6 +191,20 @@ auto with_supersample(uint32_t ss, F &&f) {
     case 8: return f(std::integral_constant<int, 8>{});
     default: return f(std::integral_constant<int, 1>{});
   }
+}
+/* option "sky_filter" (0 or 1 -- the option's writer admits nothing else) as a type */
+template <typename F>
+auto with_filter(uint32_t filter, F &&f) {
+  return filter ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+}
+/* the filter indexes the virtual sky of 256 w x 256 h texels with 32-bit numbers */
+constexpr uint32_t kSkyFilterMaxSide = 1u << 23;
+/* a render call with the filter on: both skies must be small enough for that */
+inline int check_sky_filter_sizes(curvis_ctx *ctx) {
+  for (const auto &sky : ctx->sky)
+    if (sky.texels && (sky.w > kSkyFilterMaxSide || sky.h > kSkyFilterMaxSide))
+      return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: a sky of more than 2^23 texels per side (256 times its size must fit 32 bits)");
+  return CURVIS_OK;
 }
 inline unsigned supersample_log2(uint32_t ss) { return ss == 8 ? 3u : ss == 4 ? 2u : ss == 2 ? 1u : 0u; }
 /* the cameras of a supersampled call: the same sensor at ss times the resolution (pixel (ss x, ss y) of it is pixel (x, y) of the
@@ -362,9 +378,9 @@ unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
 }
 
 /* grid = fresh workgroups + relay workgroups; see geodesic_relay */
-template <int KIND, bool FAST, int SS>
+template <int KIND, bool FAST, int SS, int FILTER>
 int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
-  void (*const kernel)(const IntegrateParams, const RelayArgs) = geodesic_relay<KIND, FAST, SS>;
+  void (*const kernel)(const IntegrateParams, const RelayArgs) = geodesic_relay<KIND, FAST, SS, FILTER>;
   const size_t bytes = sizeof(RelayQueue) + sizeof(unsigned) * kRelayRing;
   if (int rc = ctx->d_rq.reserve(ctx, bytes)) return rc;
   RelayArgs A;
@@ -391,7 +407,7 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
     std::memset(ctx->relay_resident_blocks, 0, sizeof ctx->relay_resident_blocks);
     ctx->relay_resident_threads = (int)bt;
   }
-  unsigned &cached = ctx->relay_resident_blocks[supersample_log2(SS)][KIND][FAST ? 1 : 0];
+  unsigned &cached = ctx->relay_resident_blocks[FILTER][supersample_log2(SS)][KIND][FAST ? 1 : 0];
   if (cached == 0) {
     int per_cu = 0;
     HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)bt, 0));
@@ -410,20 +426,20 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
   return CURVIS_OK;
 }
 
-/* a supersampled launch (render_impl admits it on the fused paths only): the relay kernel, or the static one */
-template <int KIND, bool FAST, int SS>
+/* a supersampled or filtered launch (render_impl admits either on the fused paths only): the relay kernel, or the static one */
+template <int KIND, bool FAST, int SS, int FILTER>
 int launch_integrate_ss(curvis_ctx *ctx, const IntegrateParams &P, int relay) {
-  if (relay) return launch_relay<KIND, FAST, SS>(ctx, P, relay == 2);
+  if (relay) return launch_relay<KIND, FAST, SS, FILTER>(ctx, P, relay == 2);
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const unsigned long long blocks = (P.total_rays + bt - 1ull) / bt;
-  hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS>), dim3((unsigned)blocks), dim3(bt), 0, ctx->stream, P);
+  hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER>), dim3((unsigned)blocks), dim3(bt), 0, ctx->stream, P);
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
 
 template <int KIND, bool PHI, bool FAST>
 int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int relay) {
-  if (relay && fused) return launch_relay<KIND, FAST, 1>(ctx, P, relay == 2);
+  if (relay && fused) return launch_relay<KIND, FAST, 1, 0>(ctx, P, relay == 2);
   if (ctx->variant != 0) {
     const unsigned bt = integrate_block_threads(ctx, KIND);
     const unsigned long long blocks = (P.total_rays + bt - 1ull) / bt;
@@ -449,15 +465,18 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int 
 
 
 /* phi is integrated for the debug dump only, which is never fused and never relayed */
-int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P, uint32_t ss) {
+int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P, uint32_t ss,
+                         uint32_t filter) {
   return with_kind(kind, [&](auto K) {
     constexpr int KIND = decltype(K)::value;
-    if (ss > 1)
+    if (ss > 1 || filter)
       return with_flag(fast, [&](auto F) {
         return with_supersample(ss, [&](auto N) {
-          constexpr int SS = decltype(N)::value;
-          if constexpr (SS > 1) return launch_integrate_ss<KIND, decltype(F)::value, SS>(ctx, P, relay);
-          else return (int)CURVIS_E_INVALID;
+          return with_filter(filter, [&](auto L) {
+            constexpr int SS = decltype(N)::value, FILTER = decltype(L)::value;
+            if constexpr (SS > 1 || FILTER != 0) return launch_integrate_ss<KIND, decltype(F)::value, SS, FILTER>(ctx, P, relay);
+            else return (int)CURVIS_E_INVALID;
+          });
         });
       });
     if (phi) return with_flag(fast, [&](auto F) { return launch_integrate<KIND, true, decltype(F)::value>(ctx, P, false, 0); });
@@ -505,16 +524,17 @@ struct BruteCall {
   uint32_t row_begin, row_count; /* row band (curvis_render_brute_rows); row_count = 0: the whole frame */
   uint32_t ss;                   /* supersampling factor.  With ss > 1 the cameras, the band, W and H are those of the ss times finer
                                     RAY grid (what the kernels run over); npix and fb_bytes are always those of the frames written */
+  uint32_t filter;               /* option "sky_filter" for this call */
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
   size_t npix = 0, fb_bytes = 0;
 };
 int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin,
-                uint32_t row_count, uint32_t ss);
+                uint32_t row_count, uint32_t ss, uint32_t filter);
 /* the same frames once more (the relay kernel's fall-backs and its checker): with the caller's outputs, or into d_fb only */
 int render_again(curvis_ctx *ctx, const BruteCall &c, bool deliver) {
   return render_rays(ctx, c.metric, c.cams, c.n_frames, c.max_iter, c.max_radius, c.delta, deliver ? c.rgb_out : nullptr,
-                     deliver ? c.dbg_out : nullptr, deliver ? c.stats : nullptr, c.row_begin, c.row_count, c.ss);
+                     deliver ? c.dbg_out : nullptr, deliver ? c.stats : nullptr, c.row_begin, c.row_count, c.ss, c.filter);
 }
 /* a piece's answer when the relay kernel has just been switched off for this context (waves that gave up, a checked launch that
  * differs): render_impl renders the call again -- the static kernel takes it */
@@ -612,7 +632,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   Q.counters = FC;
 
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P, c.ss);
+  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P, c.ss, c.filter);
   if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   if (trace) {
@@ -658,7 +678,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
     if (hq->finished >= n_tiles) break;
     if (ctx->last_relay_launches++ > 64)
       return fail(ctx, CURVIS_E_HIP, "relay kernel: tiles still unfinished after 64 relay launches");
-    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P, c.ss);
+    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P, c.ss, c.filter);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
@@ -716,9 +736,10 @@ struct LastRenderStats {
  * reports it on stderr, counts it ("relay_mismatches"), switches the context to the static kernel and asks for the call to be
  * rendered again (kRenderAgain): the caller gets the static kernel's frame.  Called after a relay render, d_fb holding its frames. */
 int relay_seat_belt(curvis_ctx *ctx, const BruteCall &c) {
-  /* everything that shapes the hand-over pattern: size of the ray grid and frame count, metric, step flavour and supersampling
-   * factor (another epilogue), the band, the step cap, the segment length and hop limit in force */
-  const std::array<uint32_t, 9> shape = {c.W, c.H, c.n_frames, (uint32_t)c.metric->kind, (uint32_t)(ctx->fast_math != 0 ? 1 : 0) | (c.ss << 8),
+  /* everything that shapes the hand-over pattern: size of the ray grid and frame count, metric, step flavour, supersampling
+   * factor and sky filter (other epilogues), the band, the step cap, the segment length and hop limit in force */
+  const std::array<uint32_t, 9> shape = {c.W, c.H, c.n_frames, (uint32_t)c.metric->kind,
+                                         (uint32_t)(ctx->fast_math != 0 ? 1 : 0) | (c.ss << 8) | (c.filter << 16),
                                          c.row_begin, c.row_count, c.max_iter,
                                          (uint32_t)ctx->relay_segment * 256u + (uint32_t)std::max(0, ctx->relay_max_hops)};
   bool auto_check = false;
@@ -797,13 +818,14 @@ void replay_debug_time(const BruteCall &c) {
 /* cameras, band and `ss` as BruteCall has them: in units of the ray grid */
 int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames,
                 uint32_t max_iterations, double max_radius, double delta, uint8_t *rgb_out,
-                curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin, uint32_t row_count, uint32_t ss) {
+                curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin, uint32_t row_count, uint32_t ss,
+                uint32_t filter) {
   if (!ctx) return CURVIS_E_INVALID;
   if (!metric || !cams || n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   const auto t_begin = std::chrono::steady_clock::now();
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
-  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, ss};
+  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, ss, filter};
   const uint32_t H_full = cams[0].res_y;
   c.W = cams[0].res_x;
   if (c.W == 0 || H_full == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
@@ -874,9 +896,18 @@ int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
 int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
-  const uint32_t ss = ctx ? (uint32_t)ctx->supersample : 1u;
+  const uint32_t ss = ctx ? (uint32_t)ctx->supersample : 1u, filter = ctx ? (uint32_t)ctx->sky_filter : 0u;
+  if (filter && metric && cams && n_frames) { /* option "sky_filter" = 1: the fused epilogues hold the filtered lookup, nothing else does */
+    if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)");
+    if (ctx->variant == 0)
+      return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only");
+    if (ctx->fuse_shade == 0)
+      return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only");
+    if (int rc = check_sky_filter_sizes(ctx)) return rc;
+  }
   if (ss <= 1u || !metric || !cams || n_frames == 0)
-    return render_rays(ctx, metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u);
+    return render_rays(ctx, metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u,
+                       filter);
   if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)");
   if (ctx->variant == 0)
     return fail(ctx, CURVIS_E_INVALID, "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve");
@@ -886,7 +917,7 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
   if (!supersampled_cameras(cams, n_frames, ss, fine) || (uint64_t)row_begin * ss > 0xFFFFFFFFull || (uint64_t)row_count * ss > 0xFFFFFFFFull)
     return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
   return render_rays(ctx, metric, fine.data(), n_frames, max_iterations, max_radius, delta, rgb_out, nullptr, stats, row_begin * ss,
-                     row_count * ss, ss);
+                     row_count * ss, ss, filter);
 }
 
 }  // namespace

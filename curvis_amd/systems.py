@@ -254,6 +254,19 @@ class SphericalImage:
         """src/images.rs:171-174: Rgba of the texel the world-space direction v points at"""
         return self.get_pixel(*self.pixel_index_from_vector3(v))
 
+    def bilinear_taps_from_vector3(self, v):
+        """what library option "sky_filter" = 1 blends for the world-space direction v (curvis_sky_bilinear_taps):
+        ((x0, x1, y0, y1, fx, fy), (tx, ty), in_bounds) -- columns, rows and the weights of x1 and y1 in 1/256, the nearest lookup's raw
+        indices, and whether these lie inside the image"""
+        from .algebra import Orientation
+        inv = np.ascontiguousarray(Orientation(self.forward, self.up).inverse_rotation_matrix().reshape(9))
+        vv = _vec(v, 3)
+        taps, raw = (C.c_uint32 * 6)(), (C.c_uint32 * 2)()
+        rc = lib().curvis_sky_bilinear_taps(self.width_pixels, self.height_pixels, dptr(inv), dptr(vv), taps, raw)
+        if rc != 0 and (self.width_pixels > 1 << 23 or self.height_pixels > 1 << 23):
+            raise ValueError("sky_filter: an image of more than 2^23 texels per side")
+        return tuple(taps), tuple(raw), rc == 0
+
 
 class HostBuffer:
     """page-locked host memory (curvis_host_alloc) as a uint8 numpy array `.array`: the device-to-host copy of a render
@@ -655,6 +668,21 @@ class Context:
                                                 out.ctypes.data_as(C.POINTER(C.c_uint32))), self._h)
         return out
 
+    def selftest_sky_bilinear(self, rgba, dirs, inv_rot=None):
+        """the filtered sky lookup of the kernels (option "sky_filter" = 1) on n directions (n x 3) for the h x w x 4 uint8 image
+        `rgba` with inverse rotation inv_rot (default: identity): (taps uint32 [n, 2, 6] = x0, x1, y0, y1, fx, fy; rgb uint8
+        [n, 2, 3]) -- index 0 of the second axis as the brute / direct renderers compute them, 1 as the efficient renderer's
+        per-pixel kernel does (curvis_selftest_sky_bilinear)"""
+        img = np.ascontiguousarray(rgba, dtype=np.uint8)
+        assert img.ndim == 3 and img.shape[2] == 4
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        inv = np.ascontiguousarray(np.eye(3) if inv_rot is None else inv_rot, dtype=np.float64).reshape(9)
+        taps = np.zeros((d.shape[0], 2, 6), dtype=np.uint32)
+        rgb = np.zeros((d.shape[0], 2, 3), dtype=np.uint8)
+        check(lib().curvis_selftest_sky_bilinear(self._h, img.shape[1], img.shape[0], dptr(inv), img.ctypes.data, dptr(d), d.shape[0],
+                                                 taps.ctypes.data_as(C.POINTER(C.c_uint32)), rgb.ctypes.data), self._h)
+        return taps, rgb
+
 
 _default_ctx = {}
 
@@ -725,26 +753,40 @@ def check_supersample(supersample):
     return int(supersample)
 
 
-class _Supersampled:
-    """the context's "supersample" option set to `factor` for the duration of a render call, then put back"""
+SKY_FILTERS = ("nearest", "bilinear")  # the values of library option "sky_filter", 0 and 1
 
-    def __init__(self, context, factor):
-        self.context, self.factor = context, factor
+
+def check_sky_filter(sky_filter):
+    """the sky lookup as the library option's value, or ValueError: "nearest" (0, the reference's) or "bilinear" (1)"""
+    if not isinstance(sky_filter, str) or sky_filter not in SKY_FILTERS:
+        raise ValueError("sky_filter must be 'nearest' or 'bilinear'")
+    return SKY_FILTERS.index(sky_filter)
+
+
+class _Supersampled:
+    """the context's "supersample" option set to `factor` -- and "sky_filter" to `sky_filter` (0 or 1) -- for the duration of a render
+    call, then put back"""
+
+    def __init__(self, context, factor, sky_filter=0):
+        self.context, self.want = context, (("supersample", factor), ("sky_filter", sky_filter))
 
     def __enter__(self):
-        self.before = self.context.get_option("supersample")
-        if self.before != self.factor:
-            self.context.set_option("supersample", self.factor)
+        self.before = [self.context.get_option(key) for key, _ in self.want]
+        for (key, value), before in zip(self.want, self.before):
+            if before != value:
+                self.context.set_option(key, value)
 
     def __exit__(self, *exc):
-        if self.before != self.factor:
-            self.context.set_option("supersample", self.before)
+        for (key, value), before in zip(self.want, self.before):
+            if before != value:
+                self.context.set_option(key, before)
         return False
 
 
 class RelativisticSystem:
     """RelativisticSystem<M> (src/systems.rs:68-73).  The three renderers take supersample=N (1, 2, 4 or 8; not in the
-    reference): N x N rays per pixel, averaged on the device into the camera's resolution."""
+    reference): N x N rays per pixel, averaged on the device into the camera's resolution; and sky_filter="nearest" (the
+    reference's lookup) or "bilinear" (not in the reference: the four texels around a ray's direction, blended on the device)."""
 
     def __init__(self, metric, background_positive, background_negative, camera, context=None):
         self.metric = metric
@@ -761,34 +803,34 @@ class RelativisticSystem:
         if ctx._sky_objs[1] is not self.background_negative:
             ctx.set_sky(1, self.background_negative)
 
-    def render_image(self, max_iterations, max_radius, delta, supersample=1):
+    def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest"):
         """The per-pixel renderer; returns an HxWx3 uint8 array (DynamicImage::ImageRgb8)."""
-        factor = check_supersample(supersample)
+        factor, filt = check_supersample(supersample), check_sky_filter(sky_filter)
         self._bind_skies()
-        with _Supersampled(self.context, factor):
+        with _Supersampled(self.context, factor, filt):
             rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
         self.last_stats = st
         return rgb
 
     def render_image_efficient(self, max_iterations_propagation, max_radius, delta, alpha_nums,
                                max_iterations_sampling, sampling_convergence_threshold_1,
-                               sampling_convergence_threshold_2, supersample=1):
+                               sampling_convergence_threshold_2, supersample=1, sky_filter="nearest"):
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
-        factor = check_supersample(supersample)
+        factor, filt = check_supersample(supersample), check_sky_filter(sky_filter)
         self._bind_skies()
-        with _Supersampled(self.context, factor):
+        with _Supersampled(self.context, factor, filt):
             rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
                                                     alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
                                                     sampling_convergence_threshold_2)
         self.last_stats = st
         return rgb
 
-    def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1):
+    def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest"):
         """NOT in the reference: the image render_image_efficient approximates, with compute_escape_angle evaluated
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
-        factor = check_supersample(supersample)
+        factor, filt = check_supersample(supersample), check_sky_filter(sky_filter)
         self._bind_skies()
-        with _Supersampled(self.context, factor):
+        with _Supersampled(self.context, factor, filt):
             rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
         self.last_stats = st
         return rgb

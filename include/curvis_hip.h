@@ -194,6 +194,12 @@ int curvis_update_relativistic_object(const curvis_metric *metric, double x[4], 
  * Returns CURVIS_OK, or CURVIS_E_INVALID with the indices still set when x == w or y == h (the reference's
  * get_pixel panics there; the kernels clamp and count such rays, curvis_stats.n_oob). */
 int curvis_sky_texel_index(uint32_t w, uint32_t h, const double inv_rot[9], const double v[3], uint32_t *x, uint32_t *y);
+/* its sibling for option "sky_filter" = 1 (host only): steps 1-4 of the option's definition below for the direction v --
+ * taps = {x0, x1, y0, y1, fx, fy}, raw = {X >> 8, Y >> 8} (what curvis_sky_texel_index returns for the same arguments).
+ * Returns CURVIS_OK, or CURVIS_E_INVALID with the outputs still set when the ray is out of bounds (raw[0] >= w or raw[1] >= h),
+ * and CURVIS_E_INVALID for w or h beyond 2^23 (raw set, taps zero: 256 w is no u32 any more). */
+int curvis_sky_bilinear_taps(uint32_t w, uint32_t h, const double inv_rot[9], const double v[3], uint32_t taps[6] /* x0 x1 y0 y1 fx fy */,
+                             uint32_t raw[2] /* X>>8, Y>>8 */);
 
 /* A band of image rows [row_begin, row_begin + row_count) of the same frame: rays are independent
  * (src/systems.rs:316-326), so a single image can be split across GPUs by rows and assembled on the host
@@ -383,6 +389,26 @@ int curvis_ctx_download_wait(curvis_ctx *ctx);
  * the efficient and direct renderers; a row band is given in output rows.  Framebuffer, downloads and the PNG front end see
  * res_x x res_y frames.  Refused with CURVIS_E_INVALID while N > 1: curvis_render_brute_debug (one record per ray),
  * "variant" = 0 and "fuse_shade" = 0 (rays staged one by one: no tile-local resolve)),
+ * "sky_filter" (0 = nearest, the default and the reference's lookup bit for bit, or 1 = bilinear; anything else is refused with
+ * CURVIS_E_INVALID "sky_filter must be 0 (nearest) or 1 (bilinear)" and the old value stays.  For a ray that escapes to a sky of
+ * w x h RGBA8 texels T[y][x] with final direction d:
+ *   1. (X, Y) are the raw `as u32` indices that the nearest lookup returns for a sky of 256 w x 256 h texels with the same
+ *      orientation: its floating-point sequence with (double)(256 w) and (double)(256 h) in place of (double)w and (double)h and
+ *      nothing else changed (the efficient renderer's instantiation with the call's reciprocals included).  Multiplying by a power
+ *      of two commutes with rounding, so X >> 8 and Y >> 8 are the nearest lookup's raw tx and ty, bit for bit: the filter costs no
+ *      additional FP64 operation, and the nearest texel of a filtered ray is the reference's.
+ *   2. The ray is out of bounds exactly when X >> 8 >= w or Y >> 8 >= h -- the same rays as with the filter off, counted in n_oob
+ *      as there.  Then Xc = min(X, 256 w - 1) and Yc = min(Y, 256 h - 1).
+ *   3. Longitude wraps around the seam, with texel centres at 256 x + 128: U = Xc - 128 if Xc >= 128, else Xc + 256 w - 128;
+ *      x0 = U >> 8, fx = U & 255, x1 = x0 + 1, or 0 when that equals w.
+ *   4. Colatitude clamps at the poles: V = max(Yc - 128, 0); y0 = V >> 8, fy = V & 255, y1 = min(y0 + 1, h - 1).
+ *   5. For each of R, G and B: out = ((256 - fx)(256 - fy) T[y0][x0] + fx (256 - fy) T[y0][x1] + (256 - fx) fy T[y1][x0]
+ *      + fx fy T[y1][x1] + 32768) >> 16.  The weights are integers that sum to 65536, the whole expression fits 32 bits, and half
+ *      rounds up; alpha is ignored.  (Not a two-stage lerp with intermediate rounding.)
+ * Capped rays stay black, and all counters are those of the nearest render.  With "supersample" = N every sub-ray is filtered and
+ * the N x N box average is taken over the filtered colours.  A render call with the filter on and a sky wider or taller than 2^23
+ * texels fails with CURVIS_E_INVALID (256 w must stay a u32); so do, as under supersampling, curvis_render_brute_debug,
+ * "variant" = 0 and "fuse_shade" = 0.  Sampler prefetch, PNG front end, downloads, row bands and batches are untouched),
  * "max_store_bytes" (ray-store budget that bounds the frames per launch of a batch),
  * "sampling_speculation" (efficient renderer: depth of the speculative dyadic subtree evaluated below every
  * refined interval; 0 = one launch per refinement round; default -1 = automatic, 10 for one or two frames, 6 for three to five and 4
@@ -436,6 +462,13 @@ int curvis_selftest_fast_step(curvis_ctx *ctx, const curvis_metric *metric, doub
  * values, BEFORE the clamp to w - 1 / h - 1 (ty == h for a direction on the -z axis).  tests/test_gpu_sky_lookup.py. */
 int curvis_selftest_sky_indices(curvis_ctx *ctx, uint32_t w, uint32_t h, const double inv_rot[9], const double *dirs, size_t n,
                                 uint32_t *out);
+
+/* the filtered lookup of option "sky_filter" = 1 as the kernels compile it, on chosen directions: rgba is a HOST image of w x h
+ * RGBA8 texels (w * h * 4 bytes), dirs = n x {d0, d1, d2}; out_taps: n x 2 x {x0, x1, y0, y1, fx, fy}, out_rgb: n x 2 x {r, g, b} --
+ * first as the brute and direct renderers compute them, then as the efficient renderer's per-pixel kernel does (shared
+ * reciprocals, as in curvis_selftest_sky_indices).  tests/test_gpu_sky_filter.py. */
+int curvis_selftest_sky_bilinear(curvis_ctx *ctx, uint32_t w, uint32_t h, const double inv_rot[9], const uint8_t *rgba, const double *dirs,
+                                 size_t n, uint32_t *out_taps, uint8_t *out_rgb);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ of each.  Needs no GPU.
 
 A kernel's text is everything between its label and its .Lfunc_end label, with the assembler's function-local label numbers
 (.LBB<n>_, .Lfunc_end<n>, .Ltmp<n>) renumbered: they count the functions of the file and shift when one is added.  A kernel
-template that gained a trailing template parameter is compared, in its instantiation with that parameter = 1, with its old self.
+template that gained a trailing template parameter is compared, in its instantiation with that parameter at its default (1 for a
+factor, 0 for a switch), with its old self; so is a kernel that became a template with one such parameter.
 Exit status 1 when a kernel present on both sides differs."""
 import argparse
 import difflib
@@ -66,13 +67,15 @@ def main():
     a = ap.parse_args()
     (b0, u0), (b1, u1) = kernels_of(a.before), kernels_of(a.after)
     names = demangle(sorted(set(b0) | set(b1)))
-    # a kernel template that gained a trailing template parameter whose default, 1, is what it was before: paired with its old name
+    # a kernel template that gained a trailing template parameter whose default (1: a factor, 0: a switch) is what it was before, or
+    # a kernel that became a template with such a parameter (then "void name<0>(...)"): paired with its old name
     old_of = {names[n]: n for n in b0}
-    for n in [n for n in b1 if n not in b0]:
-        was = old_of.get(re.sub(r", 1>\(", ">(", names[n], count=1))
-        if was is not None and was not in b1:
-            b1[was], u1[was] = b1.pop(n), u1.pop(n, {})
-            names[was] = names.pop(n)
+    for pattern, to in ((r", 0>\(", ">("), (r"^void (.*)<0>\(", r"\1("), (r", 1>\(", ">(")):
+        for n in [n for n in b1 if n not in b0 and re.search(pattern, names[n])]:
+            was = old_of.get(re.sub(pattern, to, names[n], count=1))
+            if was is not None and was not in b1:
+                b1[was], u1[was] = b1.pop(n), u1.pop(n, {})
+                names[was] = names.pop(n)
     fmt = lambda u: "VGPR %s AGPR %s SGPR %s occupancy %s LDS %s scratch %s" % tuple(  # noqa: E731
         u.get(k, "?") for k in ("VGPRs", "AGPRs", "TotalSGPRs", "Occupancy", "LDS", "ScratchSize"))
     differ = 0
