@@ -1,12 +1,16 @@
 /* curvis_hip.hip -- the ONE translation unit of libcurvis_hip.so (C ABI: include/curvis_hip.h), gfx950 only.
  *
  * Pieces (each included here and nowhere else; `make asm` before/after the split: the same instructions):
+ *   kernels_epilogue.h   what the render kernels share behind their loops: per-frame counters and a wave's reduction into them,
+ *                        direction -> colour (sky_lookup_bilinear, shade_ray's sky_lookup), colour -> frame buffer (store_rgb8, resolve_store)
  *   kernels_geodesic.h   device side of RelativisticSystem::render_image (src/systems.rs:307-330, rows R1-R10 of SURVEY.md 8a)
  *   kernels_efficient.h  device side of render_image_efficient (src/systems.rs:333-527), direct mode, trajectories, math self-test
  *   hip_owned.h          the owners of the HIP resources (device / page-locked buffers, events, streams, sky textures): what a
  *                        context or a call holds is freed by destructors, on every return path
- *   render_host.h        struct curvis_ctx, with_kind / with_flag (metric kind and step flavour -> template arguments), kernel
- *                        selection, render_impl = path decision + render_chunk + relay_seat_belt, per-frame statistics
+ *   render_host.h        struct curvis_ctx, with_kind / with_flag (metric kind and step flavour -> template arguments) and
+ *                        with_launch_shape (those two, supersample and sky_filter -> one tag type), prepare_call_shape (what the
+ *                        two options make of a call, for all three renderers), kernel selection, render_impl = path decision +
+ *                        render_chunk + relay_seat_belt, per-frame statistics
  *   efficient_host.h     the adaptive sampler's driver (src/sampling.rs) over batched escape-angle launches, the device sampler's
  *                        slots and prefetch, per-pixel launch and statistics shared by the two
  *   kernels_png.h, png_host.h   PNG front end on the device: the frames in HBM -> one zlib stream per frame (src/rendering.rs:110, :311)
@@ -29,7 +33,7 @@
  *   escape_angle_kernel<KIND,FAST>, efficient_pixel_kernel, direct_kernel, trajectory_kernel   efficient mode and extras.
  *   geodesic_static / geodesic_relay / direct_kernel<..., SS>, efficient_pixel_ss_kernel<SS>   option "supersample" = SS in
  *       {2, 4, 8} (SS = 1: the kernels above): the same kernels over the SS times finer ray grid; the wave that holds an 8x8 tile of it averages every SS x SS
- *       block across its lanes (DPP / ds_swizzle / ds_bpermute) and stores one pixel per block (resolve_store).
+ *       block across its lanes (DPP / ds_swizzle / ds_bpermute) and stores one pixel per block (kernels_epilogue.h resolve_store).
  *   the same with a trailing FILTER = 1 (efficient_pixel_kernel<1>, efficient_pixel_ss_kernel<SS, 1>)   option "sky_filter" = 1: the
  *       epilogues blend the four texels around the direction (cv_device.h sky_bilinear_taps / sky_bilinear_blend) instead of
  *       fetching the nearest; FILTER = 0 are the kernels above, instruction for instruction.
@@ -79,6 +83,7 @@
 
 #pragma clang fp contract(off)
 
+#include "kernels_epilogue.h"
 #include "kernels_geodesic.h"
 #include "kernels_efficient.h"
 #include "hip_owned.h"

@@ -144,23 +144,15 @@ int make_pixel_params(curvis_ctx *ctx, uint32_t n_frames, uint32_t W, uint32_t H
 
 /* K3 over n_frames frames of Q.W x Q.H pixels: linear pixel order, or -- supersampled -- 8x8 tiles of the fine grid, four per workgroup */
 int launch_pixel_kernel(curvis_ctx *ctx, const EfficientPixelParams &Q, uint32_t n_frames, uint32_t ss, uint32_t filter) {
-  if (ss > 1u) {
-    const unsigned long long tiles = (unsigned long long)((Q.W + 7u) / 8u) * ((Q.H + 7u) / 8u);
-    if ((tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
-    with_supersample(ss, [&](auto N) {
-      with_filter(filter, [&](auto L) {
-        constexpr int SS = decltype(N)::value, FILTER = decltype(L)::value;
-        if constexpr (SS > 1)
-          hipLaunchKernelGGL((efficient_pixel_ss_kernel<SS, FILTER>), dim3((unsigned)((tiles + 3ull) / 4ull), n_frames), dim3(256), 0,
-                             ctx->stream, Q);
-      });
-    });
-  } else {
-    const size_t npix = (size_t)Q.W * Q.H;
-    with_filter(filter, [&](auto L) {
-      hipLaunchKernelGGL(efficient_pixel_kernel<decltype(L)::value>, dim3((unsigned)((npix + 255) / 256), n_frames), dim3(256), 0, ctx->stream, Q);
-    });
-  }
+  const unsigned long long tiles = (unsigned long long)((Q.W + 7u) / 8u) * ((Q.H + 7u) / 8u);
+  if (ss > 1u && (tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
+  const unsigned long long groups = ss > 1u ? (tiles + 3ull) / 4ull : ((unsigned long long)Q.W * Q.H + 255ull) / 256ull;
+  with_launch_shape(0, false, ss, filter, [&](auto S) { /* the metric kind and the step flavour mean nothing to K3 */
+    using T = decltype(S);
+    const dim3 grid((unsigned)groups, n_frames);
+    if constexpr (T::SS > 1) hipLaunchKernelGGL((efficient_pixel_ss_kernel<T::SS, T::FILTER>), grid, dim3(256), 0, ctx->stream, Q);
+    else hipLaunchKernelGGL(efficient_pixel_kernel<T::FILTER>, grid, dim3(256), 0, ctx->stream, Q);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
@@ -859,18 +851,13 @@ int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *r
   if (!ctx) return CURVIS_E_INVALID;
   if (!call.metric || !call.cams || call.n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   /* option "supersample" = N > 1: the call over the N times finer pixel grid (the samplers see camera radii only and do not notice),
-   * averaged into res_x x res_y frames by the per-pixel kernel; "rays" are fine pixels */
+   * averaged into res_x x res_y frames by the per-pixel kernel; "rays" are fine pixels;
+   * option "sky_filter" = 1: the per-pixel kernel blends; the samplers never see a sky */
   EfficientCall c = call;
-  if (ctx->sky_filter) { /* option "sky_filter" = 1: the per-pixel kernel blends; the samplers never see a sky */
-    if (int rc = check_sky_filter_sizes(ctx)) return rc;
-    c.filter = 1u;
-  }
-  std::vector<curvis_camera> fine;
-  if (ctx->supersample > 1) {
-    c.ss = (uint32_t)ctx->supersample;
-    if (!supersampled_cameras(call.cams, call.n_frames, c.ss, fine)) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
-    c.cams = fine.data();
-  }
+  CallShape shape;
+  if (int rc = prepare_call_shape(ctx, c.cams, c.n_frames, "frame or batch too large", shape)) return rc;
+  c.ss = shape.ss;
+  c.filter = shape.filter;
   const curvis_metric *metric = c.metric;
   const curvis_camera *cams = c.cams;
   const uint32_t n_frames = c.n_frames, alpha_nums = c.alpha_nums;
@@ -947,14 +934,9 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   /* option "supersample" = N > 1: the camera of the N times finer grid, averaged into res_x x res_y by the kernel's epilogue */
-  const uint32_t ss = (uint32_t)ctx->supersample, filter = (uint32_t)ctx->sky_filter;
-  if (filter)
-    if (int rc2 = check_sky_filter_sizes(ctx)) return rc2;
-  std::vector<curvis_camera> fine;
-  if (ss > 1u) {
-    if (!supersampled_cameras(cam, 1, ss, fine)) return fail(ctx, CURVIS_E_INVALID, "frame too large");
-    cam = fine.data();
-  }
+  CallShape shape;
+  if ((rc = prepare_call_shape(ctx, cam, 1, "frame too large", shape))) return rc;
+  const uint32_t ss = shape.ss, filter = shape.filter;
   const uint32_t W = cam->res_x, H = cam->res_y;
   if (W == 0 || H == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
   if (std::fabs(cam->pos[1]) > max_radius)
@@ -988,17 +970,10 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   P.counters = FC;
   const size_t cnt_words = counter_words(1, FC.slots);
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  with_kind(metric->kind, [&](auto K) {
-    with_flag(ctx->fast_math != 0, [&](auto F) {
-      with_supersample(ss, [&](auto N) {
-        with_filter(filter, [&](auto L) {
-          constexpr int KIND = decltype(K)::value, SS = decltype(N)::value, FILTER = decltype(L)::value;
-          constexpr bool FAST = decltype(F)::value;
-          const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
-          hipLaunchKernelGGL((direct_kernel<KIND, FAST, SS, FILTER>), grid, dim3(256), 0, ctx->stream, P);
-        });
-      });
-    });
+  with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, [&](auto S) {
+    using T = decltype(S);
+    const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
+    hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER>), grid, dim3(256), 0, ctx->stream, P);
   });
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));

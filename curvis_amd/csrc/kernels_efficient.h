@@ -297,7 +297,7 @@ __global__ void recip_chain_kernel(const double *d, double *y, unsigned n) {
  * `curvis video` in the reference's default mode.  (Walking several groups per workgroup to reduce even less often was worse: the
  * compiler hoists the frame's constants out of the loop into 155 VGPRs -- 3 waves per SIMD instead of 8 --, and as a
  * non-inlined call the body spills.)  The RGB8 bytes of a wave's 64 pixels are transposed through LDS and stored as 48 dwords. */
-template <int FILTER = 0> /* option "sky_filter": 0 nearest texel, 1 bilinear (sky_lookup_bilinear, kernels_geodesic.h) */
+template <int FILTER = 0> /* option "sky_filter": 0 nearest texel, 1 bilinear */
 __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPixelParams P) {
   __shared__ __attribute__((aligned(16))) unsigned char s_rgb[256 * 3];
   __shared__ unsigned s_cnt[5];
@@ -349,10 +349,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
     __builtin_amdgcn_wave_barrier(); /* LDS operations of one wave complete in order; the buffer is this wave's alone */
     if (lane < 48u) reinterpret_cast<unsigned *>(fb + (size_t)(pix - lane) * 3u)[lane] = reinterpret_cast<const unsigned *>(sw)[lane];
   } else if (valid) {
-    unsigned char *dst = fb + (size_t)pix * 3u;
-    dst[0] = (unsigned char)(texel & 0xFF);
-    dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-    dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+    store_rgb8(fb + (size_t)pix * 3u, texel);
   }
   /* statistics: ballots per wave, LDS across the waves, one lane of the workgroup for the frame's counters */
   const unsigned n_pos = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(pos)), n_neg = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(neg));
@@ -378,9 +375,13 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
 
 /* K3 with supersampling (option "supersample" = SS in {2, 4, 8}): P.W x P.H, the cameras and the shared reciprocals are those of
  * the SS times finer grid, and fine pixels are enumerated by 8x8 tiles -- one per wave, four per workgroup, the frame in blockIdx.y --
- * instead of linearly, so that the wave holding a tile averages its SS x SS blocks into the W/SS x H/SS frame (resolve_store,
- * kernels_geodesic.h).  Per fine pixel it is efficient_pixel_kernel: the same interpolation, the same wave-level sky branches, the
- * same per-workgroup statistics (counted in fine pixels). */
+ * instead of linearly, so that the wave holding a tile averages its SS x SS blocks into the W/SS x H/SS frame (resolve_store).
+ * Per fine pixel it is efficient_pixel_kernel: the same interpolation, the same wave-level sky branches, the same
+ * per-workgroup statistics (counted in fine pixels).  All three are written out in both kernels, for measured reasons: the
+ * interpolation and the sky branches as one function, even an inlined one, make the compiler fetch every kernel argument up front
+ * (106 SGPRs instead of 76, seven waves per SIMD instead of eight); the lookup as shade_ray's sky_lookup and the statistics as a
+ * function each change the instructions of all eight instantiations (register allocation, waits; 20 to 120 lines each), which
+ * would need a timing against the parent that has not been made. */
 template <int SS, int FILTER = 0>
 __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const EfficientPixelParams P) {
   __shared__ unsigned s_cnt[5];
@@ -503,6 +504,8 @@ void direct_kernel(const DirectParams P) {
       cvk::efficient_final_direction(P.frame, axis, angle, fin);
       const cvk::SkyParams &S = P.sky[code == cvk::CODE_POS ? 0 : 1];
       unsigned tx, ty;
+      /* shade_ray's sky_lookup (kernels_epilogue.h) written out: called from here it reorders the values live across the Euler loop
+       * above, and the registers of its floating-point instructions change with them (up to 450 changed lines per instantiation) */
       if constexpr (FILTER != 0) {
         if (sky_lookup_bilinear<false>(S, fin[0], fin[1], fin[2], tx, ty, texel)) oob = 1;
       } else {
@@ -519,9 +522,7 @@ void direct_kernel(const DirectParams P) {
     }
     if constexpr (SS == 1) {
       unsigned char *dst = P.fb + ((size_t)py * P.W + px) * 3;
-      dst[0] = (unsigned char)(texel & 0xFF);
-      dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-      dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+      store_rgb8(dst, texel);
     } else {
       texel_ss = texel;
     }

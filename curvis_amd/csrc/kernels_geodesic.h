@@ -1,107 +1,9 @@
-/* kernels_geodesic.h -- the per-pixel path on the device: per-frame counters, launch parameters,
+/* kernels_geodesic.h -- the per-pixel path on the device: launch parameters,
  * geodesic_static / geodesic_persistent / geodesic_relay, the relay seat belt's compare kernel, shade_kernel.
  * Part of the ONE translation unit curvis_hip.hip (included there, nowhere else). */
 #pragma once
 
 namespace {
-
-
-/* Statistics counters, PER FRAME (src/rendering.rs:291-316 renders frame by frame; BASELINE configs[4] asks for
- * per-frame early-termination statistics, and a batch of frames is ONE launch here).  Layout of the counter block,
- * in 128-byte lines of CNT_STRIDE words: line 0 holds the persistent kernel's queue head (CNT_NEXT) and nothing
- * else; then `slots` replica lines per frame, each {FC_STEPS, FC_RAYS, FC_POS, FC_NEG, FC_NONE, FC_OOB}.  A wave
- * adds its sums to the replica (blockIdx.x mod slots) of its frame: tens of thousands of waves adding to ONE
- * address serialise in a single L2 channel (it made the 0.06 ms per-pixel kernel of the efficient renderer take
- * 0.40 ms), so a frame's counters are spread over 64 lines in launches of a few frames and over 8 in larger
- * batches.  The host sums the replicas of a frame, and the frames for the totals of the call. */
-enum { CNT_NEXT = 0 };
-enum { FC_STEPS = 0, FC_RAYS, FC_POS, FC_NEG, FC_NONE, FC_OOB, FC_N };
-enum { CNT_STRIDE = 16 };
-struct FrameCounters {
-  unsigned long long *base; /* device: CNT_STRIDE * (1 + n_frames * slots) words */
-  unsigned slots;           /* replica lines per frame, a power of two */
-};
-__host__ __device__ inline unsigned counter_slots_for(unsigned n_frames) { return n_frames >= 8u ? 8u : 64u; }
-__host__ __device__ inline size_t counter_words(unsigned n_frames, unsigned slots) {
-  return (size_t)CNT_STRIDE * (1u + (size_t)n_frames * slots);
-}
-__device__ __forceinline__ unsigned long long *frame_counter_line(const FrameCounters &C, unsigned frame) {
-  return C.base + (size_t)CNT_STRIDE * (1u + (size_t)frame * C.slots + (blockIdx.x & (C.slots - 1u)));
-}
-/* frame of a wave's 8x8 tile, as a scalar: computed in the epilogue from the wave-uniform tile number so that no
- * per-lane frame index stays live across the Euler loop (it cost the Interstellar relay kernel its fifth wave) */
-__device__ __forceinline__ unsigned frame_of_tile(unsigned long long tile, unsigned rays_per_frame) {
-  const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)tile); /* tiles < 2^32 (checked on the host) */
-  return t / (rays_per_frame >> 6);
-}
-/* Add a wave's contribution to the per-frame counters.  `frame` is per lane; lanes with !valid contribute
- * nothing.  When every valid lane of the wave belongs to one frame (always true for the 8x8-tile kernels, and for
- * all but the waves straddling a frame boundary in the per-pixel kernels) the wave reduces first and one lane
- * issues the atomics; otherwise each valid lane adds its own. */
-__device__ __forceinline__ void flush_frame_counts(const FrameCounters &C, unsigned frame, bool valid,
-                                                   unsigned long long steps, unsigned rays, unsigned pos, unsigned neg,
-                                                   unsigned none, unsigned oob) {
-  const unsigned long long vm = __builtin_amdgcn_ballot_w64(valid);
-  if (!vm) return;
-  const unsigned f0 = (unsigned)__builtin_amdgcn_readlane((int)frame, (int)__builtin_ctzll(vm));
-  if (!valid) steps = 0ull, rays = pos = neg = none = oob = 0u;
-  if (__builtin_amdgcn_ballot_w64(valid && frame != f0) == 0ull) {
-    for (int off = 32; off > 0; off >>= 1) {
-      steps += __shfl_xor(steps, off);
-      rays += __shfl_xor(rays, off);
-      pos += __shfl_xor(pos, off);
-      neg += __shfl_xor(neg, off);
-      none += __shfl_xor(none, off);
-      oob += __shfl_xor(oob, off);
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-      unsigned long long *c = frame_counter_line(C, f0);
-      if (steps) atomicAdd(&c[FC_STEPS], steps);
-      if (rays) atomicAdd(&c[FC_RAYS], (unsigned long long)rays);
-      if (pos) atomicAdd(&c[FC_POS], (unsigned long long)pos);
-      if (neg) atomicAdd(&c[FC_NEG], (unsigned long long)neg);
-      if (none) atomicAdd(&c[FC_NONE], (unsigned long long)none);
-      if (oob) atomicAdd(&c[FC_OOB], (unsigned long long)oob);
-    }
-  } else if (valid) {
-    unsigned long long *c = frame_counter_line(C, frame);
-    if (steps) atomicAdd(&c[FC_STEPS], steps);
-    if (rays) atomicAdd(&c[FC_RAYS], (unsigned long long)rays);
-    if (pos) atomicAdd(&c[FC_POS], (unsigned long long)pos);
-    if (neg) atomicAdd(&c[FC_NEG], (unsigned long long)neg);
-    if (none) atomicAdd(&c[FC_NONE], (unsigned long long)none);
-    if (oob) atomicAdd(&c[FC_OOB], (unsigned long long)oob);
-  }
-}
-
-/* the same for kernels whose lanes contribute FLAGS (one pixel each, no step counts): four ballots and population counts per
- * wave instead of 42 cross-lane shuffles -- the per-pixel kernel of the efficient renderer runs ~1 000 instructions per pixel,
- * the generic reduction was ~5 % of them */
-__device__ __forceinline__ void flush_frame_flags(const FrameCounters &C, unsigned frame, bool valid, bool pos, bool neg, bool none,
-                                                  bool oob) {
-  const unsigned long long vm = __builtin_amdgcn_ballot_w64(valid);
-  if (!vm) return;
-  const unsigned f0 = (unsigned)__builtin_amdgcn_readlane((int)frame, (int)__builtin_ctzll(vm));
-  if (__builtin_amdgcn_ballot_w64(valid && frame != f0) == 0ull) {
-    const unsigned n_pos = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid && pos)), n_neg = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid && neg));
-    const unsigned n_none = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid && none)), n_oob = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(valid && oob));
-    if ((threadIdx.x & 63u) == 0u) {
-      unsigned long long *c = frame_counter_line(C, f0);
-      atomicAdd(&c[FC_RAYS], (unsigned long long)__popcll(vm));
-      if (n_pos) atomicAdd(&c[FC_POS], (unsigned long long)n_pos);
-      if (n_neg) atomicAdd(&c[FC_NEG], (unsigned long long)n_neg);
-      if (n_none) atomicAdd(&c[FC_NONE], (unsigned long long)n_none);
-      if (n_oob) atomicAdd(&c[FC_OOB], (unsigned long long)n_oob);
-    }
-  } else if (valid) { /* a wave that straddles two frames: every lane for itself */
-    unsigned long long *c = frame_counter_line(C, frame);
-    atomicAdd(&c[FC_RAYS], 1ull);
-    if (pos) atomicAdd(&c[FC_POS], 1ull);
-    if (neg) atomicAdd(&c[FC_NEG], 1ull);
-    if (none) atomicAdd(&c[FC_NONE], 1ull);
-    if (oob) atomicAdd(&c[FC_OOB], 1ull);
-  }
-}
 
 /* Final ray states, structure-of-arrays in HBM, indexed by pixel id = frame*W*H + py*W + px.
  * Written by the integration kernel, read once by the shading kernel (48-56 B per ray against
@@ -232,22 +134,6 @@ __device__ __forceinline__ void one_step(const cvk::MetricParams &M, double delt
     cvk::ray_step<KIND, PHI, MathTablesLds<KIND>::WIDE_SC>(M, q, delta);
 }
 
-/* option "sky_filter" = 1: the blend of the four texels around the direction instead of the nearest one (cv_device.h
- * sky_bilinear_taps / sky_bilinear_blend).  The four gathers are independent of each other: all are issued before the blend
- * waits for the first.  tx, ty and the return value (out of bounds) are those of the nearest lookup. */
-template <bool SHARED>
-__device__ __forceinline__ bool sky_lookup_bilinear(const cvk::SkyParams &S, double d0, double d1, double d2, unsigned &tx, unsigned &ty,
-                                                    unsigned &texel, double y_pi = 0.0, double y_two_pi = 0.0) {
-  cvk::SkyTaps t;
-  cvk::sky_bilinear_taps<SHARED>(S, d0, d1, d2, t, y_pi, y_two_pi);
-  const unsigned *row0 = S.texels + (size_t)t.y0 * S.w, *row1 = S.texels + (size_t)t.y1 * S.w;
-  const unsigned t00 = row0[t.x0], t01 = row0[t.x1], t10 = row1[t.x0], t11 = row1[t.x1];
-  texel = cvk::sky_bilinear_blend(t00, t01, t10, t11, t.fx, t.fy);
-  tx = t.tx;
-  ty = t.ty;
-  return t.oob;
-}
-
 /* final photon -> tangent direction -> nearest sky texel (rows R9-R10 of SURVEY.md 8a); FILTER: the bilinear blend instead */
 template <int KIND, int FILTER = 0>
 __device__ __forceinline__ unsigned shade_ray(const cvk::MetricParams &M, const cvk::SkyParams *sky, const cvk::Ray &q,
@@ -257,65 +143,9 @@ __device__ __forceinline__ unsigned shade_ray(const cvk::MetricParams &M, const 
   if (code != cvk::CODE_NONE) {
     double d0, d1, d2;
     cvk::ray_direction<KIND>(M, q, d0, d1, d2);
-    const cvk::SkyParams &S = sky[code == cvk::CODE_POS ? 0 : 1];
-    if constexpr (FILTER != 0) {
-      if (sky_lookup_bilinear<false>(S, d0, d1, d2, tx, ty, texel)) oob = 1;
-      return texel;
-    }
-    cvk::sky_indices(S, d0, d1, d2, tx, ty);
-    unsigned cx = tx, cy = ty;
-    if (cx >= S.w || cy >= S.h) oob = 1; /* reference: image::get_pixel panics; defined here: clamp + count */
-    if (cx >= S.w) cx = S.w - 1;
-    if (cy >= S.h) cy = S.h - 1;
-    texel = S.texels[(size_t)cy * S.w + cx];
+    sky_lookup<FILTER>(sky[code == cvk::CODE_POS ? 0 : 1], d0, d1, d2, tx, ty, texel, oob);
   }
   return texel;
-}
-
-/* ---- supersampling (option "supersample" = SS in {2, 4, 8}): the launch runs over the SS x SS times finer ray grid, and the
- * wave that holds an 8x8 tile of it averages every SS x SS block into one output pixel.  SS divides 8, so a block never straddles
- * two waves: no atomics, no second pass.  Lane k of a tile is sub-pixel (k & 7, k >> 3), so the lanes of a block differ in the low
- * log2 SS bits of each half of the lane number: xor masks {1, 8}, {1, 2, 8, 16}, {1, 2, 4, 8, 16, 32}.
- *
- * v of lane (lane ^ MASK).  Every lane of the wave must be active: DPP for the masks that stay inside a row of 16 lanes
- * (quad_perm [1,0,3,2] and [2,3,0,1], row_ror:8), ds_swizzle in bit mode (and 0x1f, xor MASK) inside a half wave, ds_bpermute
- * across the two halves -- none of them touches LDS memory. */
-template <unsigned MASK>
-__device__ __forceinline__ unsigned lane_xor(unsigned v) {
-  static_assert(MASK == 1u || MASK == 2u || MASK == 4u || MASK == 8u || MASK == 16u || MASK == 32u, "one bit of the lane number");
-  if (MASK == 1u) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
-  if (MASK == 2u) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);
-  if (MASK == 8u) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);
-  if (MASK == 4u || MASK == 16u) return (unsigned)__builtin_amdgcn_ds_swizzle((int)v, (int)((MASK << 10) | 0x1Fu));
-  return (unsigned)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 63u) ^ 32u) << 2), (int)v);
-}
-
-/* Called by EVERY lane of a wave that holds one 8x8 tile of the fine grid: (px, py) is the lane's fine pixel inside the launch,
- * W x H the fine size of the launch (multiples of SS), `texel` what the lane's ray saw; lanes with !valid (outside the frame: whole
- * blocks of them, since SS divides 8) add nothing.  Channel sums are at most 64 x 255 < 2^14: red and green share a dword.  The
- * lane of sub-pixel (0, 0) of each block stores out = (sum + SS^2 / 2) >> (2 log2 SS) -- the straight average of the 8-bit values,
- * half rounded up -- at pixel (px / SS, py / SS) of frame `frame` of the W/SS x H/SS frames in fb. */
-template <int SS>
-__device__ __forceinline__ void resolve_store(unsigned char *fb, unsigned W, unsigned H, unsigned frame, unsigned px, unsigned py,
-                                              bool valid, unsigned texel) {
-  static_assert(SS == 2 || SS == 4 || SS == 8, "a wave's 64 rays are an 8x8 tile: the factor must divide 8");
-  constexpr unsigned LG = SS == 2 ? 1u : SS == 4 ? 2u : 3u;
-  unsigned rg = valid ? ((texel & 0xFFu) | ((texel & 0xFF00u) << 8)) : 0u;
-  unsigned b = valid ? ((texel >> 16) & 0xFFu) : 0u;
-  rg += lane_xor<1>(rg), b += lane_xor<1>(b);
-  if (SS >= 4) rg += lane_xor<2>(rg), b += lane_xor<2>(b);
-  if (SS >= 8) rg += lane_xor<4>(rg), b += lane_xor<4>(b);
-  rg += lane_xor<8>(rg), b += lane_xor<8>(b);
-  if (SS >= 4) rg += lane_xor<16>(rg), b += lane_xor<16>(b);
-  if (SS >= 8) rg += lane_xor<32>(rg), b += lane_xor<32>(b);
-  if (valid && ((px | py) & (unsigned)(SS - 1)) == 0u) {
-    constexpr unsigned HALF = (unsigned)(SS * SS) / 2u;
-    const unsigned Wo = W >> LG, Ho = H >> LG;
-    unsigned char *dst = fb + ((size_t)frame * Wo * Ho + (size_t)(py >> LG) * Wo + (px >> LG)) * 3;
-    dst[0] = (unsigned char)(((rg & 0xFFFFu) + HALF) >> (2u * LG));
-    dst[1] = (unsigned char)(((rg >> 16) + HALF) >> (2u * LG));
-    dst[2] = (unsigned char)((b + HALF) >> (2u * LG));
-  }
 }
 
 /* K1, persistent form: lanes draw rays from a global queue with one wave-aggregated atomic whenever
@@ -398,7 +228,7 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
  * final state in HBM for shade_kernel -- the epilogue needs fewer registers than the loop, so the fusion is
  * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame.
  * SS: supersampling factor (1: one ray per output pixel; 2, 4, 8: P is in units of the fine grid and the epilogue averages,
- * resolve_store above; FUSED only). */
+ * kernels_epilogue.h resolve_store; FUSED only). */
 template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0> /* FILTER: option "sky_filter" (FUSED only) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
 void geodesic_static(const IntegrateParams P) {
@@ -455,33 +285,22 @@ void geodesic_static(const IntegrateParams P) {
   const unsigned long long id2 = (unsigned long long)bid * blockDim.x + threadIdx.x;
   valid = id2 < P.total_rays && decode_ray(P, id2, frame, px, py);
   const size_t slot = valid ? (size_t)frame * P.W * P.H + (size_t)py * P.W + px : 0;
-  if constexpr (SS == 1) {
-    if (valid) {
-      if (FUSED) {
-        unsigned tx, ty;
-        const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
-        unsigned char *dst = P.fb + slot * 3;
-        dst[0] = (unsigned char)(texel & 0xFF);
-        dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-        dst[2] = (unsigned char)((texel >> 16) & 0xFF);
-        pos = (code == cvk::CODE_POS);
-        neg = (code == cvk::CODE_NEG);
-        none = (code == cvk::CODE_NONE);
-      } else {
-        store_ray<PHI>(P.store, slot, q, steps, code);
-      }
-    }
-  } else {
-    unsigned texel = 0u;
-    if (valid) {
+  [[maybe_unused]] unsigned seen = 0u; /* SS > 1: what the lane's ray saw, for the resolve behind the branch */
+  if (valid) {
+    if (FUSED) {
       unsigned tx, ty;
-      texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
+      const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
+      /* the plain store in THIS branch: the compiler does not merge a second test of `valid` behind the shading with the first */
+      if constexpr (SS == 1) store_rgb8(P.fb + slot * 3, texel);
+      else seen = texel;
       pos = (code == cvk::CODE_POS);
       neg = (code == cvk::CODE_NEG);
       none = (code == cvk::CODE_NONE);
+    } else {
+      store_ray<PHI>(P.store, slot, q, steps, code);
     }
-    resolve_store<SS>(P.fb, P.W, P.H, frame, px, py, valid, texel); /* the whole wave: lanes outside the frame add nothing */
   }
+  if constexpr (SS > 1) resolve_store<SS>(P.fb, P.W, P.H, frame, px, py, valid, seen); /* the whole wave: lanes outside the frame add nothing */
   /* statistics of the wave's tile go to the counters of ITS frame (a tile never straddles frames); on the staged
    * path shade_kernel keeps them */
   if (FUSED) flush_frame_counts(P.counters, frame_of_tile(id2 >> 6, P.rays_per_frame), valid, steps, 1u, pos, neg, none, oob);
@@ -703,31 +522,18 @@ void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
     unsigned tile_s = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)tile);
     asm volatile("" : "+s"(tile_s));
     const unsigned long long id2 = (unsigned long long)tile_s * 64ull + lane;
-    if constexpr (SS == 1) {
-      unsigned frame2, px2, py2;
-      if (id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2)) {
-        unsigned tx, ty;
-        const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
-        unsigned char *dst = P.fb + ((size_t)frame2 * P.W * P.H + (size_t)py2 * P.W + px2) * 3;
-        dst[0] = (unsigned char)(texel & 0xFF);
-        dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-        dst[2] = (unsigned char)((texel >> 16) & 0xFF);
-        pos = (code == cvk::CODE_POS);
-        neg = (code == cvk::CODE_NEG);
-        none = (code == cvk::CODE_NONE);
-      }
-    } else { /* the wave that finishes a tile holds all 64 of its rays, parked on the way or not: it averages them */
-      unsigned frame2 = 0, px2 = 0, py2 = 0, texel = 0u;
-      const bool valid2 = id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2);
-      if (valid2) {
-        unsigned tx, ty;
-        texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
-        pos = (code == cvk::CODE_POS);
-        neg = (code == cvk::CODE_NEG);
-        none = (code == cvk::CODE_NONE);
-      }
-      resolve_store<SS>(P.fb, P.W, P.H, frame2, px2, py2, valid2, texel);
+    unsigned frame2 = 0, px2 = 0, py2 = 0, texel = 0u;
+    const bool valid2 = id2 < P.total_rays && decode_ray(P, id2, frame2, px2, py2);
+    if (valid2) {
+      unsigned tx, ty;
+      texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
+      if constexpr (SS == 1) store_rgb8(P.fb + ((size_t)frame2 * P.W * P.H + (size_t)py2 * P.W + px2) * 3, texel); /* as in geodesic_static */
+      pos = (code == cvk::CODE_POS);
+      neg = (code == cvk::CODE_NEG);
+      none = (code == cvk::CODE_NONE);
     }
+    /* the wave that finishes a tile holds all 64 of its rays, parked on the way or not: supersampled, it averages them */
+    if constexpr (SS > 1) resolve_store<SS>(P.fb, P.W, P.H, frame2, px2, py2, valid2, texel);
     if (lane == 0 && tile < A.n_tiles) atomicAdd(&Q->finished, 1ull);
   }
   /* a tile is counted once, by the wave that finishes it, in the counters of its frame */
@@ -781,10 +587,7 @@ __global__ __launch_bounds__(256) void shade_kernel(const ShadeParams P) {
     M.LT = cv_log_table();
     M.AT = cv_atan_table();
     const unsigned texel = shade_ray<KIND>(M, P.sky, q, code, tx, ty, oob);
-    unsigned char *dst = P.fb + o * 3;
-    dst[0] = (unsigned char)(texel & 0xFF);
-    dst[1] = (unsigned char)((texel >> 8) & 0xFF);
-    dst[2] = (unsigned char)((texel >> 16) & 0xFF);
+    store_rgb8(P.fb + o * 3, texel);
     pos = (code == cvk::CODE_POS);
     neg = (code == cvk::CODE_NEG);
     none = (code == cvk::CODE_NONE);

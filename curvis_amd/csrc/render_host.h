@@ -100,7 +100,7 @@ struct curvis_ctx {
   int fast_math = 1;        /* 1 shared-reciprocal step (ray_step_fast), 0 compiler IEEE div/sqrt */
   int fuse_shade = 1;       /* static kernel shades in its epilogue (no ray store, no shade launch) */
   int supersample = 1;      /* N in {1, 2, 4, 8}: every render call traces N x N rays per pixel of the cameras' resolution and the
-                               kernels' epilogues average them (kernels_geodesic.h resolve_store); frames stay res_x x res_y */
+                               kernels' epilogues average them (kernels_epilogue.h resolve_store); frames stay res_x x res_y */
   int sky_filter = 0;       /* 0: a ray takes the nearest sky texel (the reference); 1: the bilinear blend of the four around its
                                direction, defined in include/curvis_hip.h (cv_device.h sky_bilinear_taps / sky_bilinear_blend) */
   int sampling_speculation = -1; /* efficient renderer: depth of the speculative subtree evaluated below every
@@ -182,41 +182,61 @@ template <typename F>
 auto with_flag(bool flag, F &&f) {
   return flag ? f(std::true_type{}) : f(std::false_type{});
 }
-/* the supersampling factor (option "supersample": 1, 2, 4 or 8 -- the option's writer admits nothing else) as a type */
+/* The whole shape of a render launch -- metric kind, step flavour, supersampling factor, sky filter -- as ONE type:
+ * with_launch_shape(kind, fast, ss, filter, [&](auto S) { using T = decltype(S); ... T::KIND, T::FAST, T::SS, T::FILTER ... }) calls the
+ * lambda once.  ss is 1, 2, 4 or 8 and filter 0 or 1: the writers of the options "supersample" and "sky_filter" admit nothing else. */
+template <int KIND_, bool FAST_, int SS_, int FILTER_>
+struct LaunchShape {
+  static constexpr int KIND = KIND_, SS = SS_, FILTER = FILTER_;
+  static constexpr bool FAST = FAST_;
+};
 template <typename F>
-auto with_supersample(uint32_t ss, F &&f) {
-  switch (ss) {
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 8: return f(std::integral_constant<int, 8>{});
-    default: return f(std::integral_constant<int, 1>{});
-  }
-}
-/* option "sky_filter" (0 or 1 -- the option's writer admits nothing else) as a type */
-template <typename F>
-auto with_filter(uint32_t filter, F &&f) {
-  return filter ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
-}
-/* the filter indexes the virtual sky of 256 w x 256 h texels with 32-bit numbers */
-constexpr uint32_t kSkyFilterMaxSide = 1u << 23;
-/* a render call with the filter on: both skies must be small enough for that */
-inline int check_sky_filter_sizes(curvis_ctx *ctx) {
-  for (const auto &sky : ctx->sky)
-    if (sky.texels && (sky.w > kSkyFilterMaxSide || sky.h > kSkyFilterMaxSide))
-      return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: a sky of more than 2^23 texels per side (256 times its size must fit 32 bits)");
-  return CURVIS_OK;
+auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, F &&f) {
+  return with_kind(kind, [&](auto K) {
+    return with_flag(fast, [&](auto A) {
+      auto with_ss = [&](auto N) {
+        constexpr int KIND = decltype(K)::value, SS = decltype(N)::value;
+        constexpr bool FAST = decltype(A)::value;
+        return filter ? f(LaunchShape<KIND, FAST, SS, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0>{});
+      };
+      switch (ss) {
+        case 2: return with_ss(std::integral_constant<int, 2>{});
+        case 4: return with_ss(std::integral_constant<int, 4>{});
+        case 8: return with_ss(std::integral_constant<int, 8>{});
+        default: return with_ss(std::integral_constant<int, 1>{});
+      }
+    });
+  });
 }
 inline unsigned supersample_log2(uint32_t ss) { return ss == 8 ? 3u : ss == 4 ? 2u : ss == 2 ? 1u : 0u; }
-/* the cameras of a supersampled call: the same sensor at ss times the resolution (pixel (ss x, ss y) of it is pixel (x, y) of the
- * original, cv_device.h ray_init); false when a resolution no longer fits 32 bits */
-inline bool supersampled_cameras(const curvis_camera *cams, uint32_t n_frames, uint32_t ss, std::vector<curvis_camera> &out) {
-  out.assign(cams, cams + n_frames);
-  for (curvis_camera &c : out) {
-    if ((uint64_t)c.res_x * ss > 0xFFFFFFFFull || (uint64_t)c.res_y * ss > 0xFFFFFFFFull) return false;
-    c.res_x *= ss;
-    c.res_y *= ss;
+
+/* the filter indexes the virtual sky of 256 w x 256 h texels with 32-bit numbers */
+constexpr uint32_t kSkyFilterMaxSide = 1u << 23;
+/* What the options "supersample" and "sky_filter" make of a render call, for all three renderers: the factor, the filter, and
+ * -- ss > 1 -- the cameras of the call over the ss times finer grid: the same sensor at ss times the resolution (pixel (ss x, ss y)
+ * of it is pixel (x, y) of the original, cv_device.h ray_init). */
+struct CallShape {
+  uint32_t ss = 1, filter = 0;
+  std::vector<curvis_camera> fine;
+};
+/* cams: the caller's n_frames cameras on entry, those the kernels run over on return (s.fine with ss > 1).  With the filter on, both
+ * skies must be small enough for it; too_large is the renderer's message for a fine resolution that no longer fits 32 bits. */
+int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_frames, const char *too_large, CallShape &s) {
+  s.ss = (uint32_t)ctx->supersample;
+  s.filter = (uint32_t)ctx->sky_filter;
+  if (s.filter)
+    for (const auto &sky : ctx->sky)
+      if (sky.texels && (sky.w > kSkyFilterMaxSide || sky.h > kSkyFilterMaxSide))
+        return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: a sky of more than 2^23 texels per side (256 times its size must fit 32 bits)");
+  if (s.ss <= 1u) return CURVIS_OK;
+  s.fine.assign(cams, cams + n_frames);
+  for (curvis_camera &c : s.fine) {
+    if ((uint64_t)c.res_x * s.ss > 0xFFFFFFFFull || (uint64_t)c.res_y * s.ss > 0xFFFFFFFFull) return fail(ctx, CURVIS_E_INVALID, too_large);
+    c.res_x *= s.ss;
+    c.res_y *= s.ss;
   }
-  return true;
+  cams = s.fine.data();
+  return CURVIS_OK;
 }
 
 /* ---- overlapped download of the frames (option "async_download" = 1) -------------------------------------------------
@@ -426,61 +446,45 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
   return CURVIS_OK;
 }
 
-/* a supersampled or filtered launch (render_impl admits either on the fused paths only): the relay kernel, or the static one */
-template <int KIND, bool FAST, int SS, int FILTER>
-int launch_integrate_ss(curvis_ctx *ctx, const IntegrateParams &P, int relay) {
-  if (relay) return launch_relay<KIND, FAST, SS, FILTER>(ctx, P, relay == 2);
-  const unsigned bt = integrate_block_threads(ctx, KIND);
-  const unsigned long long blocks = (P.total_rays + bt - 1ull) / bt;
-  hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER>), dim3((unsigned)blocks), dim3(bt), 0, ctx->stream, P);
-  HIP_TRY(ctx, hipGetLastError());
-  return CURVIS_OK;
-}
-
-template <int KIND, bool PHI, bool FAST>
+/* One launch of the integrator.  relay: 0 no, 1 the relay kernel, 2 its relay-only re-launch.  The unfused static kernel and the
+ * persistent one exist for SS = 1, FILTER = 0 only (their static_asserts): render_impl refuses the call shapes that would need more. */
+template <int KIND, bool PHI, bool FAST, int SS, int FILTER>
 int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int relay) {
-  if (relay && fused) return launch_relay<KIND, FAST, 1, 0>(ctx, P, relay == 2);
-  if (ctx->variant != 0) {
-    const unsigned bt = integrate_block_threads(ctx, KIND);
-    const unsigned long long blocks = (P.total_rays + bt - 1ull) / bt;
-    if (fused)
-      hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true>), dim3((unsigned)blocks), dim3(bt), 0, ctx->stream, P);
-    else
-      hipLaunchKernelGGL((geodesic_static<KIND, PHI, FAST, false>), dim3((unsigned)blocks), dim3(bt), 0, ctx->stream, P);
-  } else {
-    int per_cu = ctx->blocks_per_cu;
-    if (per_cu <= 0) {
-      HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, geodesic_persistent<KIND, PHI, FAST>, 256, 0));
-      if (per_cu <= 0) per_cu = 1;
+  if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER>(ctx, P, relay == 2);
+  const unsigned bt = integrate_block_threads(ctx, KIND);
+  const dim3 grid((unsigned)((P.total_rays + bt - 1ull) / bt));
+  bool staged = false; /* launched a kernel that leaves the shading to shade_kernel */
+  if constexpr (SS == 1 && FILTER == 0) {
+    if (ctx->variant == 0) {
+      int per_cu = ctx->blocks_per_cu;
+      if (per_cu <= 0) {
+        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, geodesic_persistent<KIND, PHI, FAST>, 256, 0));
+        if (per_cu <= 0) per_cu = 1;
+      }
+      unsigned long long blocks = (unsigned long long)per_cu * (unsigned long long)ctx->prop.multiProcessorCount;
+      const unsigned long long max_useful = (P.total_rays + 255ull) / 256ull;
+      if (blocks > max_useful) blocks = max_useful;
+      if (blocks == 0) blocks = 1;
+      hipLaunchKernelGGL((geodesic_persistent<KIND, PHI, FAST>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
+      staged = true;
+    } else if (!fused) {
+      hipLaunchKernelGGL((geodesic_static<KIND, PHI, FAST, false>), grid, dim3(bt), 0, ctx->stream, P);
+      staged = true;
     }
-    unsigned long long blocks = (unsigned long long)per_cu * (unsigned long long)ctx->prop.multiProcessorCount;
-    const unsigned long long max_useful = (P.total_rays + 255ull) / 256ull;
-    if (blocks > max_useful) blocks = max_useful;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL((geodesic_persistent<KIND, PHI, FAST>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
   }
+  if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER>), grid, dim3(bt), 0, ctx->stream, P);
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
 
-
-/* phi is integrated for the debug dump only, which is never fused and never relayed */
+/* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled and never filtered */
 int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P, uint32_t ss,
                          uint32_t filter) {
-  return with_kind(kind, [&](auto K) {
-    constexpr int KIND = decltype(K)::value;
-    if (ss > 1 || filter)
-      return with_flag(fast, [&](auto F) {
-        return with_supersample(ss, [&](auto N) {
-          return with_filter(filter, [&](auto L) {
-            constexpr int SS = decltype(N)::value, FILTER = decltype(L)::value;
-            if constexpr (SS > 1 || FILTER != 0) return launch_integrate_ss<KIND, decltype(F)::value, SS, FILTER>(ctx, P, relay);
-            else return (int)CURVIS_E_INVALID;
-          });
-        });
-      });
-    if (phi) return with_flag(fast, [&](auto F) { return launch_integrate<KIND, true, decltype(F)::value>(ctx, P, false, 0); });
-    return with_flag(fast, [&](auto F) { return launch_integrate<KIND, false, decltype(F)::value>(ctx, P, fused, relay); });
+  return with_launch_shape(kind, fast, ss, filter, [&](auto S) {
+    using T = decltype(S);
+    if constexpr (T::SS == 1 && T::FILTER == 0)
+      if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0>(ctx, P, false, 0);
+    return launch_integrate<T::KIND, false, T::FAST, T::SS, T::FILTER>(ctx, P, fused, relay);
   });
 }
 
@@ -528,13 +532,11 @@ struct BruteCall {
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
   size_t npix = 0, fb_bytes = 0;
 };
-int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
-                double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin,
-                uint32_t row_count, uint32_t ss, uint32_t filter);
+int render_rays(curvis_ctx *ctx, BruteCall c);
 /* the same frames once more (the relay kernel's fall-backs and its checker): with the caller's outputs, or into d_fb only */
-int render_again(curvis_ctx *ctx, const BruteCall &c, bool deliver) {
-  return render_rays(ctx, c.metric, c.cams, c.n_frames, c.max_iter, c.max_radius, c.delta, deliver ? c.rgb_out : nullptr,
-                     deliver ? c.dbg_out : nullptr, deliver ? c.stats : nullptr, c.row_begin, c.row_count, c.ss, c.filter);
+int render_again(curvis_ctx *ctx, BruteCall c, bool deliver) {
+  if (!deliver) c.rgb_out = nullptr, c.dbg_out = nullptr, c.stats = nullptr;
+  return render_rays(ctx, c);
 }
 /* a piece's answer when the relay kernel has just been switched off for this context (waves that gave up, a checked launch that
  * differs): render_impl renders the call again -- the static kernel takes it */
@@ -815,53 +817,50 @@ void replay_debug_time(const BruteCall &c) {
   }
 }
 
-/* cameras, band and `ss` as BruteCall has them: in units of the ray grid */
-int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames,
-                uint32_t max_iterations, double max_radius, double delta, uint8_t *rgb_out,
-                curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin, uint32_t row_count, uint32_t ss,
-                uint32_t filter) {
+/* the call's arguments as the caller of render_impl gave them, except that cameras, band and `ss` are in units of the ray grid; the
+ * derived sizes (W ... fb_bytes) are worked out here */
+int render_rays(curvis_ctx *ctx, BruteCall c) {
   if (!ctx) return CURVIS_E_INVALID;
-  if (!metric || !cams || n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
+  if (!c.metric || !c.cams || c.n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   const auto t_begin = std::chrono::steady_clock::now();
-  int rc = curvis_metric_validate(metric);
+  int rc = curvis_metric_validate(c.metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
-  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, ss, filter};
-  const uint32_t H_full = cams[0].res_y;
-  c.W = cams[0].res_x;
+  const uint32_t H_full = c.cams[0].res_y;
+  c.W = c.cams[0].res_x;
   if (c.W == 0 || H_full == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
   /* row band (curvis_render_brute_rows): the launch covers image rows [row_begin, row_begin + row_count); the
    * cameras keep the full resolution, which is what pixel -> direction uses */
-  const bool band = row_count != 0;
-  if (band && ((uint64_t)row_begin + row_count > H_full || n_frames != 1 || dbg_out))
+  const bool band = c.row_count != 0;
+  if (band && ((uint64_t)c.row_begin + c.row_count > H_full || c.n_frames != 1 || c.dbg_out))
     return fail(ctx, CURVIS_E_INVALID, "row band outside the frame (or used with a batch / the debug dump)");
-  c.H = band ? row_count : H_full;
-  for (uint32_t f = 0; f < n_frames; ++f) {
-    if (cams[f].res_x != c.W || cams[f].res_y != H_full)
+  c.H = band ? c.row_count : H_full;
+  for (uint32_t f = 0; f < c.n_frames; ++f) {
+    if (c.cams[f].res_x != c.W || c.cams[f].res_y != H_full)
       return fail(ctx, CURVIS_E_INVALID, "all cameras of a batch must share one resolution");
-    if (std::fabs(cams[f].pos[1]) > max_radius)
+    if (std::fabs(c.cams[f].pos[1]) > c.max_radius)
       return fail(ctx, CURVIS_E_CAMERA_OUTSIDE,
                   "Photon already beyond the maximum radius. Cannot evaluate escape. (src/systems.rs:122-124)");
   }
   if (!ctx->sky[0].texels || !ctx->sky[1].texels) return fail(ctx, CURVIS_E_NO_SKY, "both background images must be set");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-  c.npix = (size_t)(c.W / ss) * (c.H / ss);
-  c.fb_bytes = c.npix * 3 * n_frames;
+  c.npix = (size_t)(c.W / c.ss) * (c.H / c.ss);
+  c.fb_bytes = c.npix * 3 * c.n_frames;
   if ((rc = fb_begin_write(ctx, c.fb_bytes))) return rc;
   ctx->fb_bytes = c.fb_bytes;
-  if (dbg_out && (rc = ctx->d_dbg.reserve(ctx, c.npix * n_frames))) return rc;
+  if (c.dbg_out && (rc = ctx->d_dbg.reserve(ctx, c.npix * c.n_frames))) return rc;
   const RenderPath path = choose_render_path(ctx, c);
   if (path.store_bytes && (rc = ctx->d_store.reserve(ctx, path.store_bytes))) return rc;
-  if ((rc = ctx->d_cams.reserve(ctx, n_frames))) return rc;
-  if ((rc = ctx->h_cams.reserve(ctx, n_frames))) return rc;
-  for (uint32_t f = 0; f < n_frames; ++f) ctx->h_cams[f] = make_camera(cams[f]);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, sizeof(cvk::CameraParams) * n_frames, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = ctx->d_cams.reserve(ctx, c.n_frames))) return rc;
+  if ((rc = ctx->h_cams.reserve(ctx, c.n_frames))) return rc;
+  for (uint32_t f = 0; f < c.n_frames; ++f) ctx->h_cams[f] = make_camera(c.cams[f]);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, sizeof(cvk::CameraParams) * c.n_frames, hipMemcpyHostToDevice, ctx->stream));
 
-  const cvk::MetricParams MP = make_metric(*metric);
+  const cvk::MetricParams MP = make_metric(*c.metric);
   RenderTotals tot;
-  ctx->last_frame_stats.assign(n_frames, curvis_stats{});
-  for (uint32_t f0 = 0; f0 < n_frames; f0 += path.chunk) {
-    rc = render_chunk(ctx, c, path, MP, f0, std::min(path.chunk, n_frames - f0), tot);
+  ctx->last_frame_stats.assign(c.n_frames, curvis_stats{});
+  for (uint32_t f0 = 0; f0 < c.n_frames; f0 += path.chunk) {
+    rc = render_chunk(ctx, c, path, MP, f0, std::min(path.chunk, c.n_frames - f0), tot);
     if (rc == kRenderAgain) return render_again(ctx, c, true);
     if (rc) return rc;
   }
@@ -872,20 +871,20 @@ int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
     if (rc == kRenderAgain) return render_again(ctx, c, true);
     if (rc) return rc;
   }
-  if (dbg_out)
-    HIP_TRY(ctx, hipMemcpyAsync(dbg_out, ctx->d_dbg, sizeof(curvis_ray_debug) * c.npix * n_frames, hipMemcpyDeviceToHost, ctx->stream));
-  if (rgb_out) {
-    if ((rc = fb_download(ctx, rgb_out, c.fb_bytes))) return rc;
+  if (c.dbg_out)
+    HIP_TRY(ctx, hipMemcpyAsync(c.dbg_out, ctx->d_dbg, sizeof(curvis_ray_debug) * c.npix * c.n_frames, hipMemcpyDeviceToHost, ctx->stream));
+  if (c.rgb_out) {
+    if ((rc = fb_download(ctx, c.rgb_out, c.fb_bytes))) return rc;
   } else {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  if (dbg_out) replay_debug_time(c);
-  if (stats) {
-    counts_to_stats(tot.counts, *stats);
-    stats->kernel_ms = tot.integrate_ms + tot.shade_ms;
-    stats->integrate_ms = tot.integrate_ms;
-    stats->shade_ms = tot.shade_ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  if (c.dbg_out) replay_debug_time(c);
+  if (c.stats) {
+    counts_to_stats(tot.counts, *c.stats);
+    c.stats->kernel_ms = tot.integrate_ms + tot.shade_ms;
+    c.stats->integrate_ms = tot.integrate_ms;
+    c.stats->shade_ms = tot.shade_ms;
+    c.stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
   return CURVIS_OK;
 }
@@ -896,28 +895,32 @@ int render_rays(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
 int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
-  const uint32_t ss = ctx ? (uint32_t)ctx->supersample : 1u, filter = ctx ? (uint32_t)ctx->sky_filter : 0u;
-  if (filter && metric && cams && n_frames) { /* option "sky_filter" = 1: the fused epilogues hold the filtered lookup, nothing else does */
-    if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)");
-    if (ctx->variant == 0)
-      return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only");
-    if (ctx->fuse_shade == 0)
-      return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only");
-    if (int rc = check_sky_filter_sizes(ctx)) return rc;
-  }
-  if (ss <= 1u || !metric || !cams || n_frames == 0)
-    return render_rays(ctx, metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u,
-                       filter);
-  if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)");
-  if (ctx->variant == 0)
-    return fail(ctx, CURVIS_E_INVALID, "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve");
-  if (ctx->fuse_shade == 0)
-    return fail(ctx, CURVIS_E_INVALID, "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve");
-  std::vector<curvis_camera> fine;
-  if (!supersampled_cameras(cams, n_frames, ss, fine) || (uint64_t)row_begin * ss > 0xFFFFFFFFull || (uint64_t)row_count * ss > 0xFFFFFFFFull)
+  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u};
+  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter)) return render_rays(ctx, c);
+  /* only the fused epilogues hold the filtered lookup and the tile-local resolve: three call shapes are refused, under the name of
+   * the filter when it is on, of the supersampling otherwise */
+  const bool f = ctx->sky_filter != 0;
+  const struct {
+    bool refused;
+    const char *filter, *supersample;
+  } shapes[3] = {
+      {dbg_out != nullptr, "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)",
+       "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)"},
+      {ctx->variant == 0, "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
+       "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve"},
+      {ctx->fuse_shade == 0, "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
+       "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve"}};
+  for (const auto &s : shapes)
+    if (s.refused) return fail(ctx, CURVIS_E_INVALID, f ? s.filter : s.supersample);
+  CallShape shape;
+  if (int rc = prepare_call_shape(ctx, c.cams, n_frames, "frame or batch too large", shape)) return rc;
+  c.ss = shape.ss;
+  c.filter = shape.filter;
+  if ((uint64_t)row_begin * c.ss > 0xFFFFFFFFull || (uint64_t)row_count * c.ss > 0xFFFFFFFFull)
     return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
-  return render_rays(ctx, metric, fine.data(), n_frames, max_iterations, max_radius, delta, rgb_out, nullptr, stats, row_begin * ss,
-                     row_count * ss, ss, filter);
+  c.row_begin *= c.ss;
+  c.row_count *= c.ss;
+  return render_rays(ctx, c);
 }
 
 }  // namespace
