@@ -71,6 +71,7 @@ SYMBOLS = {
     "curvis_metric_functions": (C.c_int, [C.POINTER(Metric), C.c_double, _dp, _dp, _dp]),
     "curvis_metric_tensor": (C.c_int, [C.POINTER(Metric), _dp, _dp, _dp]),
     "curvis_camera_outward_vector": (C.c_int, [C.POINTER(CameraC), C.c_uint32, C.c_uint32, _dp, _dp]),
+    "curvis_camera_outward_vector_projected": (C.c_int, [C.POINTER(CameraC), C.c_int32, C.c_uint32, C.c_uint32, _dp, _dp]),
     "curvis_vector_to_direction": (C.c_int, [C.POINTER(Metric), _dp, _dp, _dp]),
     "curvis_update_relativistic_object": (C.c_int, [C.POINTER(Metric), _dp, _dp, C.c_double]),
     "curvis_sky_texel_index": (C.c_int, [C.c_uint32, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -8,8 +8,8 @@
  *   hip_owned.h          the owners of the HIP resources (device / page-locked buffers, events, streams, sky textures): what a
  *                        context or a call holds is freed by destructors, on every return path
  *   render_host.h        struct curvis_ctx, with_kind / with_flag (metric kind and step flavour -> template arguments) and
- *                        with_launch_shape (those two, supersample and sky_filter -> one tag type), prepare_call_shape (what the
- *                        two options make of a call, for all three renderers), kernel selection, render_impl = path decision +
+ *                        with_launch_shape (those two, supersample, sky_filter and projection -> one tag type), prepare_call_shape
+ *                        (what the three options make of a call, for all three renderers), kernel selection, render_impl = path decision +
  *                        render_chunk + relay_seat_belt, per-frame statistics
  *   efficient_host.h     the adaptive sampler's driver (src/sampling.rs) over batched escape-angle launches, the device sampler's
  *                        slots and prefetch, per-pixel launch and statistics shared by the two
@@ -37,6 +37,9 @@
  *   the same with a trailing FILTER = 1 (efficient_pixel_kernel<1>, efficient_pixel_ss_kernel<SS, 1>)   option "sky_filter" = 1: the
  *       epilogues blend the four texels around the direction (cv_device.h sky_bilinear_taps / sky_bilinear_blend) instead of
  *       fetching the nearest; FILTER = 0 are the kernels above, instruction for instruction.
+ *   the same with a trailing PROJ = 1      option "projection" != 0: the prologues form the pixel's camera-space vector by
+ *       cv_device.h camera_pixel_vector's equirectangular or fisheye branch (a scalar branch on a kernel argument; nothing of it
+ *       lives into the Euler loop); PROJ = 0 are the kernels above, instruction for instruction.
  *   selftest_sky_bilinear_kernel           the two functions alone, both instantiations, on the tests' directions.
  *   selftest_math_kernel                   cv_math.h / IEEE div / sqrt / hardware seeds for the tests.
  *   selftest_sky_indices_kernel            cvk::sky_indices (direction -> texel), both instantiations, on the tests' directions.
@@ -512,6 +515,26 @@ int curvis_camera_outward_vector(const curvis_camera *camera, uint32_t px, uint3
   return CURVIS_OK;
 }
 
+int curvis_camera_outward_vector_projected(const curvis_camera *camera, int32_t projection, uint32_t px, uint32_t py, double camera_space[3],
+                                           double world_space[3]) {
+  if (!camera || camera->res_x == 0 || camera->res_y == 0 || projection < 0 || projection > 2) return CURVIS_E_INVALID;
+  /* the first half of cvk::ray_init, by the function it calls */
+  const cvk::CameraParams C = make_camera(*camera);
+  double vx, vy, vz;
+  cvk::camera_pixel_vector(C, (int)projection, px, py, vx, vy, vz);
+  const double n = std::sqrt(vx * vx + vy * vy + vz * vz);
+  vx = vx / n;
+  vy = vy / n;
+  vz = vz / n;
+  if (camera_space) {
+    camera_space[0] = vx;
+    camera_space[1] = vy;
+    camera_space[2] = vz;
+  }
+  if (world_space) cvk::mat3_vec(C.rot, vx, vy, vz, world_space[0], world_space[1], world_space[2]);
+  return CURVIS_OK;
+}
+
 int curvis_vector_to_direction(const curvis_metric *metric, const double position[4], const double p_cov[4],
                                double direction[3]) {
   if (!metric || !position || !p_cov || !direction) return CURVIS_E_INVALID;
@@ -919,6 +942,12 @@ const OptionEntry kOptions[] = {
      [](curvis_ctx *c, int64_t v) -> int {
        if (v != 0 && v != 1) return fail(c, CURVIS_E_INVALID, "sky_filter must be 0 (nearest) or 1 (bilinear)");
        c->sky_filter = (int)v;
+       return CURVIS_OK;
+     }},
+    {"projection", OPT_READ(c->projection),
+     [](curvis_ctx *c, int64_t v) -> int {
+       if (v < 0 || v > 2) return fail(c, CURVIS_E_INVALID, "projection must be 0 (perspective), 1 (equirectangular) or 2 (fisheye)");
+       c->projection = (int)v;
        return CURVIS_OK;
      }},
     OPT_RW(device_sampler, int),

@@ -508,14 +508,62 @@ CV_HD void mat3_vec(const double *m, double v0, double v1, double v2, double &o0
   o2 = (m[6] * v0 + m[7] * v1) + m[8] * v2;
 }
 
-/* pixel -> photon: src/cameras.rs:150-172 then src/metrics.rs:301-334 */
+/* ---- option "projection": pixel -> UN-NORMALISED camera-space vector (x forward, y left, z up), the one place where the three
+ * renderers and the host accessor form it (include/curvis_hip.h has the definition; every operation below is one of its steps, in
+ * its order).  0 is outward_vector_on_camera_space (src/cameras.rs:150-164) expression for expression; 1 and 2 sample the pixel at
+ * its centre, u = (2 px + 1) / (2 res_x): with SHARED (the efficient pixel kernel) that quotient is formed as (px + 0.5) / res_x --
+ * the same real number, px + 0.5 exact below 2^32 -- from the call's shared reciprocal, under div_index's contract.  sin and cos are
+ * cv_math.h's on the constant table (host and device agree bit for bit); sqrt and the other quotients are the IEEE operators.
+ * `projection` is uniform over a launch, so the switch is a scalar branch; nothing of it is live once the vector is formed.  Always inlined:
+ * its callers with a constant projection 0 are then compiled from the text they had before this function existed. */
+enum { PROJ_PERSPECTIVE = 0, PROJ_EQUIRECTANGULAR = 1, PROJ_FISHEYE = 2 };
+template <bool SHARED = false>
+__attribute__((always_inline)) CV_HD void camera_pixel_vector(const CameraParams &C, int projection, unsigned px, unsigned py, double &vx, double &vy, double &vz,
+                                                              const PixelRecips *R = nullptr) {
+  if (projection == PROJ_PERSPECTIVE) {
+    const double h = 0.5 - (SHARED ? div_index<SHARED>((double)py, C.res_y, R->y_res_y) : (double)py / C.res_y);
+    const double w = (SHARED ? div_index<SHARED>((double)px, C.res_x, R->y_res_x) : (double)px / C.res_x) - 0.5;
+    vx = C.focal * 1.0;
+    vy = -C.sensor_w * w;
+    vz = C.sensor_h * h;
+    return;
+  }
+  const double pu = SHARED ? div_index<SHARED>((double)px + 0.5, C.res_x, R->y_res_x) : (2.0 * (double)px + 1.0) / (2.0 * C.res_x);
+  const double pv = SHARED ? div_index<SHARED>((double)py + 0.5, C.res_y, R->y_res_y) : (2.0 * (double)py + 1.0) / (2.0 * C.res_y);
+  if (projection == PROJ_EQUIRECTANGULAR) {
+    const double psi = (0.5 - pu) * (2.0 * CV_PI);
+    const double th = pv * CV_PI;
+    double st, ct, sp, cp;
+    cv_sincos(th, &st, &ct);
+    cv_sincos(psi, &sp, &cp);
+    vx = st * cp;
+    vy = st * sp;
+    vz = ct;
+    return;
+  }
+  /* equidistant fisheye: image radius = focal * angle from the axis */
+  const double ys = -C.sensor_w * (pu - 0.5);
+  const double zs = C.sensor_h * (0.5 - pv);
+  const double rho = CV_SQRT(ys * ys + zs * zs);
+  if (rho == 0.0) { /* the centre pixel of an odd x odd frame */
+    vx = 1.0;
+    vy = 0.0;
+    vz = 0.0;
+    return;
+  }
+  const double b = rho / C.focal;
+  double sb, cb;
+  cv_sincos(b, &sb, &cb);
+  vx = cb;
+  vy = sb * (ys / rho);
+  vz = sb * (zs / rho);
+}
+
+/* pixel -> photon: src/cameras.rs:150-172 then src/metrics.rs:301-334; projection: camera_pixel_vector above */
 template <int KIND>
-CV_HD void ray_init(const MetricParams &M, const CameraParams &C, unsigned px, unsigned py, Ray &q) {
-  const double h = 0.5 - ((double)py / C.res_y);
-  const double w = ((double)px / C.res_x) - 0.5;
-  double vx = C.focal * 1.0;
-  double vy = -C.sensor_w * w;
-  double vz = C.sensor_h * h;
+CV_HD void ray_init(const MetricParams &M, const CameraParams &C, unsigned px, unsigned py, Ray &q, int projection = PROJ_PERSPECTIVE) {
+  double vx, vy, vz;
+  camera_pixel_vector(C, projection, px, py, vx, vy, vz);
   double n = CV_SQRT(vx * vx + vy * vy + vz * vz); /* Vector3::normalize */
   vx = vx / n;
   vy = vy / n;

@@ -212,11 +212,10 @@ CV_HD unsigned interp_index_grid(const double *x, unsigned n, double xp, const u
  * outward direction and the radial direction, and the rotation axis cam_bg x out_bg */
 template <bool SHARED = false>
 CV_HD void efficient_pixel_geometry(const CameraParams &C, const EfficientFrame &F, unsigned px, unsigned py, double &alpha,
-                                    double *axis, const PixelRecips *R = nullptr) {
-  /* outward_vector_on_world_space_from_x_y (src/cameras.rs:150-172) */
-  const double h = 0.5 - (SHARED ? div_index<SHARED>((double)py, C.res_y, R->y_res_y) : (double)py / C.res_y);
-  const double w = (SHARED ? div_index<SHARED>((double)px, C.res_x, R->y_res_x) : (double)px / C.res_x) - 0.5;
-  const double v0[3] = {C.focal * 1.0, -C.sensor_w * w, C.sensor_h * h};
+                                    double *axis, const PixelRecips *R = nullptr, int projection = PROJ_PERSPECTIVE) {
+  /* outward_vector_on_world_space_from_x_y (src/cameras.rs:150-172), or option "projection" */
+  double v0[3];
+  camera_pixel_vector<SHARED>(C, projection, px, py, v0[0], v0[1], v0[2], R);
   const double n = sqrt_plain<SHARED>(dot3(v0, v0)); /* norm3 */
   double v[3];
   unit3<SHARED>(v0, n, v);
@@ -244,9 +243,9 @@ template <bool SHARED = false>
 CV_HD void efficient_pixel(const CameraParams &C, const EfficientFrame &F, unsigned px, unsigned py,
                            const double *sx, const double *m_e, const double *c_e, const double *m_s,
                            const double *c_s, unsigned n_samples, double *fin, double &space, const PixelRecips *R = nullptr,
-                           const unsigned *grid = nullptr) {
+                           const unsigned *grid = nullptr, int projection = PROJ_PERSPECTIVE) {
   double alpha, axis[3];
-  efficient_pixel_geometry<SHARED>(C, F, px, py, alpha, axis, R);
+  efficient_pixel_geometry<SHARED>(C, F, px, py, alpha, axis, R, projection);
   double esc;
   if (n_samples == 0) { /* interp_slice on empty tables returns zeros */
     esc = 0.0;

@@ -16,6 +16,7 @@ struct EfficientCall {
   uint32_t alpha_nums, max_iterations_sampling;
   double thr1, thr2;
   uint32_t filter = 0; /* option "sky_filter" for this call */
+  uint32_t projection = 0; /* option "projection" for this call */
   uint32_t ss = 1; /* supersampling factor: with ss > 1 `cams` are those of the ss times finer pixel grid (render_efficient_impl) */
 };
 
@@ -143,15 +144,16 @@ int make_pixel_params(curvis_ctx *ctx, uint32_t n_frames, uint32_t W, uint32_t H
 }
 
 /* K3 over n_frames frames of Q.W x Q.H pixels: linear pixel order, or -- supersampled -- 8x8 tiles of the fine grid, four per workgroup */
-int launch_pixel_kernel(curvis_ctx *ctx, const EfficientPixelParams &Q, uint32_t n_frames, uint32_t ss, uint32_t filter) {
+int launch_pixel_kernel(curvis_ctx *ctx, EfficientPixelParams Q, uint32_t n_frames, uint32_t ss, uint32_t filter, uint32_t projection) {
+  Q.projection = (int)projection;
   const unsigned long long tiles = (unsigned long long)((Q.W + 7u) / 8u) * ((Q.H + 7u) / 8u);
   if (ss > 1u && (tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
   const unsigned long long groups = ss > 1u ? (tiles + 3ull) / 4ull : ((unsigned long long)Q.W * Q.H + 255ull) / 256ull;
-  with_launch_shape(0, false, ss, filter, [&](auto S) { /* the metric kind and the step flavour mean nothing to K3 */
+  with_launch_shape(0, false, ss, filter, projection, [&](auto S) { /* the metric kind and the step flavour mean nothing to K3 */
     using T = decltype(S);
     const dim3 grid((unsigned)groups, n_frames);
-    if constexpr (T::SS > 1) hipLaunchKernelGGL((efficient_pixel_ss_kernel<T::SS, T::FILTER>), grid, dim3(256), 0, ctx->stream, Q);
-    else hipLaunchKernelGGL(efficient_pixel_kernel<T::FILTER>, grid, dim3(256), 0, ctx->stream, Q);
+    if constexpr (T::SS > 1) hipLaunchKernelGGL((efficient_pixel_ss_kernel<T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, Q);
+    else hipLaunchKernelGGL((efficient_pixel_kernel<T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, Q);
   });
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
@@ -466,7 +468,7 @@ int render_efficient_device(curvis_ctx *ctx, const EfficientCall &c, const cvk::
   const PixelInputs in = {ctx->d_eff, o_cams, o_fr, S.d, S.o_tab_off, S.o_tab_n, S.o_grid_off, S.o_grid, S.o_tab[0], S.o_tab[3],
                           S.o_tab[4], S.o_tab[5], S.o_tab[6]};
   if ((rc = make_pixel_params(ctx, n_frames, W, H, FC, in, Q))) return rc;
-  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss, c.filter))) return rc;
+  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss, c.filter, c.projection))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words, hipMemcpyDeviceToHost, ctx->stream));
   const auto t_launched = std::chrono::steady_clock::now();
@@ -831,7 +833,7 @@ int render_pixels_staged(curvis_ctx *ctx, const EfficientCall &c, const std::vec
   const PixelInputs in = {ctx->d_eff, o_cams, o_fr, ctx->d_eff, o_to, o_tn, o_go, o_gr, o_sx, o_me, o_ce, o_ms, o_cs};
   if ((rc = make_pixel_params(ctx, n_frames, W, H, FC, in, Q))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss, c.filter))) return rc;
+  if ((rc = launch_pixel_kernel(ctx, Q, n_frames, c.ss, c.filter, c.projection))) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_counters, ctx->d_counters, sizeof(unsigned long long) * cnt_words,
                               hipMemcpyDeviceToHost, ctx->stream));
@@ -852,12 +854,14 @@ int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *r
   if (!call.metric || !call.cams || call.n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   /* option "supersample" = N > 1: the call over the N times finer pixel grid (the samplers see camera radii only and do not notice),
    * averaged into res_x x res_y frames by the per-pixel kernel; "rays" are fine pixels;
-   * option "sky_filter" = 1: the per-pixel kernel blends; the samplers never see a sky */
+   * option "sky_filter" = 1: the per-pixel kernel blends; the samplers never see a sky;
+   * option "projection" != 0: the per-pixel kernel forms other directions; the samplers tabulate the whole sphere as it is */
   EfficientCall c = call;
   CallShape shape;
   if (int rc = prepare_call_shape(ctx, c.cams, c.n_frames, "frame or batch too large", shape)) return rc;
   c.ss = shape.ss;
   c.filter = shape.filter;
+  c.projection = shape.projection;
   const curvis_metric *metric = c.metric;
   const curvis_camera *cams = c.cams;
   const uint32_t n_frames = c.n_frames, alpha_nums = c.alpha_nums;
@@ -934,16 +938,17 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   /* option "supersample" = N > 1: the camera of the N times finer grid, averaged into res_x x res_y by the kernel's epilogue */
+  DirectParams P;
   CallShape shape;
   if ((rc = prepare_call_shape(ctx, cam, 1, "frame too large", shape))) return rc;
   const uint32_t ss = shape.ss, filter = shape.filter;
+  P.projection = (int)shape.projection;
   const uint32_t W = cam->res_x, H = cam->res_y;
   if (W == 0 || H == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
   if (std::fabs(cam->pos[1]) > max_radius)
     return fail(ctx, CURVIS_E_CAMERA_OUTSIDE, "Photon already beyond the maximum radius. Cannot evaluate escape. (src/systems.rs:122-124)");
   if (!ctx->sky[0].texels || !ctx->sky[1].texels) return fail(ctx, CURVIS_E_NO_SKY, "both background images must be set");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DirectParams P;
   P.metric = make_metric(*metric);
   P.cam = make_camera(*cam);
   if (!cvk::efficient_frame_pose(cam->pos[2], cam->pos[3], P.frame)) /* src/systems.rs:393-397, :411 */
@@ -970,10 +975,10 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   P.counters = FC;
   const size_t cnt_words = counter_words(1, FC.slots);
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, [&](auto S) {
+  with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, shape.projection, [&](auto S) {
     using T = decltype(S);
     const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
-    hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER>), grid, dim3(256), 0, ctx->stream, P);
+    hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, P);
   });
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));

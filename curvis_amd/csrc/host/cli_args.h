@@ -18,9 +18,11 @@ struct Args {
   std::string gpu_png = "auto"; /* video: PNG front end on the device (curvis_ctx_deflate_frames): auto = with the fast writer, on, off */
   int supersample = 1; /* rays per pixel and axis, averaged on the device (library option "supersample"): 1, 2, 4 or 8 */
   int sky_filter = 0; /* sky lookup (library option "sky_filter"): 0 nearest texel, 1 bilinear */
+  int projection = 0; /* pixel -> direction (library option "projection"): 0 perspective, 1 equirectangular, 2 fisheye */
 };
 int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
 int g_sky_filter = 0;  /* Args::sky_filter, likewise */
+int g_projection = 0;  /* Args::projection, likewise */
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(code);
@@ -34,7 +36,8 @@ void usage() {
       "  common: [-m|--metric-settings <TOML FILE>] [-c|--camera-settings <TOML FILE>] [-s|--simulation-settings <TOML FILE>]\n"
       "  extensions: [--mode efficient|brute|direct] [--device N] [--devices N] [--batch B] [--stats FILE]\n"
       "              [--sky-broadcast rccl|upload] [--writers T] [--resume] [--png-level -1..9] [--gpu-png auto|on|off]\n"
-      "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n");
+      "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n"
+      "              [--projection perspective|equirectangular|fisheye]\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -87,6 +90,12 @@ Args parse_args(int argc, char **argv) {
       take(val);
       if (val != "nearest" && val != "bilinear") die("error: --sky-filter must be nearest or bilinear", 2);
       a.sky_filter = g_sky_filter = val == "bilinear" ? 1 : 0;
+    }
+    else if (key == "--projection") {
+      take(val);
+      if (val != "perspective" && val != "equirectangular" && val != "fisheye")
+        die("error: --projection must be perspective, equirectangular or fisheye", 2);
+      a.projection = g_projection = val == "fisheye" ? 2 : val == "equirectangular" ? 1 : 0;
     }
     else if (key == "-h" || key == "--help") { usage(); std::exit(0); }
     else if (!s.empty() && s[0] == '-') die("error: unexpected argument '" + s + "' found", 2);
@@ -236,6 +245,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
   }
   if (g_supersample != 1) check(curvis_ctx_set_option(ctx, "supersample", g_supersample), ctx, what);
   if (g_sky_filter != 0) check(curvis_ctx_set_option(ctx, "sky_filter", g_sky_filter), ctx, what);
+  if (g_projection != 0) check(curvis_ctx_set_option(ctx, "projection", g_projection), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {

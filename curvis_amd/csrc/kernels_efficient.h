@@ -273,6 +273,7 @@ struct EfficientPixelParams {
   const unsigned *grid;               /* kInterpGrid + 1 entries per table */
   const double *sx, *m_e, *c_e, *m_s, *c_s;
   unsigned n_frames, W, H;
+  int projection;                     /* option "projection", read by the PROJ instantiations only (in what was padding) */
   unsigned char *fb;
   FrameCounters counters;
   cvk::PixelRecips recips;            /* cv_device.h: reciprocals of the call's constant denominators (ensure_pixel_recips) */
@@ -297,7 +298,7 @@ __global__ void recip_chain_kernel(const double *d, double *y, unsigned n) {
  * `curvis video` in the reference's default mode.  (Walking several groups per workgroup to reduce even less often was worse: the
  * compiler hoists the frame's constants out of the loop into 155 VGPRs -- 3 waves per SIMD instead of 8 --, and as a
  * non-inlined call the body spills.)  The RGB8 bytes of a wave's 64 pixels are transposed through LDS and stored as 48 dwords. */
-template <int FILTER = 0> /* option "sky_filter": 0 nearest texel, 1 bilinear */
+template <int FILTER = 0, int PROJ = 0> /* option "sky_filter": 0 nearest texel, 1 bilinear; PROJ: 1 = option "projection" != 0 (P.projection) */
 __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPixelParams P) {
   __shared__ __attribute__((aligned(16))) unsigned char s_rgb[256 * 3];
   __shared__ unsigned s_cnt[5];
@@ -313,7 +314,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
     const unsigned off = P.tab_off[f], n = P.tab_n[f];
     double fin[3], space;
     cvk::efficient_pixel<true>(P.cams[f], P.frames[f], px, py, P.sx + off, P.m_e + off, P.c_e + off, P.m_s + off, P.c_s + off, n, fin, space,
-                               &P.recips, P.grid + P.grid_off[f]);
+                               &P.recips, P.grid + P.grid_off[f], PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
     /* match escape_space { 1.0 => ..., -1.0 => ..., _ => black }.  One sky after the other, each under its own branch: the lanes of
      * a wave nearly always look at the same sky, and then its rotation, size and texel pointer are scalar operands of that one
      * pass -- selecting them per lane cost 22 v_cndmask and the VGPRs to hold the result */
@@ -382,7 +383,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
  * (106 SGPRs instead of 76, seven waves per SIMD instead of eight); the lookup as shade_ray's sky_lookup and the statistics as a
  * function each change the instructions of all eight instantiations (register allocation, waits; 20 to 120 lines each), which
  * would need a timing against the parent that has not been made. */
-template <int SS, int FILTER = 0>
+template <int SS, int FILTER = 0, int PROJ = 0>
 __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const EfficientPixelParams P) {
   __shared__ unsigned s_cnt[5];
   const unsigned f = blockIdx.y;
@@ -399,7 +400,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const Efficient
     const unsigned off = P.tab_off[f], n = P.tab_n[f];
     double fin[3], space;
     cvk::efficient_pixel<true>(P.cams[f], P.frames[f], px, py, P.sx + off, P.m_e + off, P.c_e + off, P.m_s + off, P.c_s + off, n, fin, space,
-                               &P.recips, P.grid + P.grid_off[f]);
+                               &P.recips, P.grid + P.grid_off[f], PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
     pos = (space == 1.0);
     neg = (space == -1.0);
     none = !(pos || neg);
@@ -456,6 +457,7 @@ struct DirectParams {
   unsigned W, H, tiles_x, tiles_y;
   unsigned long long total_rays; /* tiles_x * tiles_y * 64 */
   unsigned max_iter;
+  int projection; /* option "projection", read by the PROJ instantiations only (in what was padding) */
   double max_radius, delta;
   int fast_ok;
   unsigned char *fb;
@@ -463,7 +465,7 @@ struct DirectParams {
 };
 
 /* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
-template <int KIND, bool FAST, int SS = 1, int FILTER = 0> /* FILTER: option "sky_filter" */
+template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0> /* FILTER: option "sky_filter", PROJ: option "projection" */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 4 : 6)))
 void direct_kernel(const DirectParams P) {
   [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */
@@ -479,7 +481,7 @@ void direct_kernel(const DirectParams P) {
   unsigned steps = 0, pos = 0, neg = 0, none = 0, oob = 0;
   if (valid) {
     double alpha, axis[3];
-    cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis);
+    cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis, nullptr, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
     double sa, ca;
     cv_sincos(alpha, &sa, &ca);
     const double p4[4] = {0.0, P.cam.pos[1], CV_PI / 2.0, 0.0};
@@ -499,7 +501,7 @@ void direct_kernel(const DirectParams P) {
     unsigned texel = 0xFF000000u; /* NotEscaped / undefined tangent rotation: black */
     double angle;
     if (code != cvk::CODE_NONE && cvk::escape_angle_of<KIND>(M, q, angle)) {
-      cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis); /* again: not kept live across the loop */
+      cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis, nullptr, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE); /* again: not kept live across the loop */
       double fin[3];
       cvk::efficient_final_direction(P.frame, axis, angle, fin);
       const cvk::SkyParams &S = P.sky[code == cvk::CODE_POS ? 0 : 1];

@@ -22,6 +22,8 @@ struct IntegrateParams {
   unsigned rays_per_frame;       /* tiles_x*tiles_y*64 (padded to whole 8x8 tiles) */
   unsigned long long total_rays; /* n_frames * rays_per_frame */
   unsigned max_iter;
+  int projection; /* option "projection" (cv_device.h camera_pixel_vector), read by the PROJ instantiations only; it sits in what was
+                     padding, so every other argument of every kernel stays where it was */
   double max_radius, delta;
   RayStore store;
   FrameCounters counters;
@@ -229,11 +231,13 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
  * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame.
  * SS: supersampling factor (1: one ray per output pixel; 2, 4, 8: P is in units of the fine grid and the epilogue averages,
  * kernels_epilogue.h resolve_store; FUSED only). */
-template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0> /* FILTER: option "sky_filter" (FUSED only) */
+template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0> /* FILTER: option "sky_filter" (FUSED only);
+  PROJ: 0 the reference's perspective mapping, 1 option "projection" != 0 (P.projection says which; FUSED only) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
 void geodesic_static(const IntegrateParams P) {
   static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");
   static_assert(FILTER == 0 || (FUSED && !PHI), "the filtered lookup exists in the fused epilogues only");
+  static_assert(PROJ == 0 || (FUSED && !PHI), "the projections exist in the fused kernels only");
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -246,7 +250,7 @@ void geodesic_static(const IntegrateParams P) {
   unsigned steps = 0;
   int code = cvk::CODE_NONE;
   if (id < P.total_rays && decode_ray(P, id, frame, px, py)) {
-    cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q);
+    cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
     lane_ok_w = FAST && P.fast_ok && cvk::ray_fast_ok(q);
     valid = true;
     active = P.max_iter != 0;
@@ -372,7 +376,7 @@ __device__ __forceinline__ T ld_sys(const T *p) { return __hip_atomic_load(const
 
 /* register budget: the Interstellar instantiation must stay at 5 waves per SIMD (<= 96 VGPRs; its LDS tables allow
  * no more anyway): left alone the allocator takes 97 and drops to four (+6 % time) */
-template <int KIND, bool FAST, int SS = 1, int FILTER = 0> /* SS: supersampling factor, FILTER: option "sky_filter", as in geodesic_static */
+template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0> /* SS: supersampling factor, FILTER: option "sky_filter", PROJ: option "projection", as in geodesic_static */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
 void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
   __shared__ MathTablesLds<KIND> s_tab;
@@ -433,7 +437,7 @@ void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
   int code = cvk::CODE_NONE;
   if (fresh) {
     if (valid) {
-      cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q);
+      cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
       active = P.max_iter != 0;
       steps = P.max_iter;
     }
@@ -441,7 +445,7 @@ void geodesic_relay(const IntegrateParams P, const RelayArgs A) {
     /* 40 B per parked ray: l, theta, p_l, p_theta and one packed {steps, code} word.  p_phi is a constant of the motion
      * (dp_phi = 0, src/metrics.rs:262-268; the loop never writes it): ray_init recomputes it -- and p_phi^2 -- from the
      * pixel, bit for bit what the parking wave held. */
-    if (valid) cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q);
+    if (valid) cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
     q.l = ld_sys(&P.store.l[id]);
     q.th = ld_sys(&P.store.th[id]);
     q.p1 = ld_sys(&P.store.p1[id]);

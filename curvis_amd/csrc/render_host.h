@@ -75,7 +75,7 @@ struct curvis_ctx {
                                        once, there is no dispatch phase, and the static kernel is as good) */
   uint32_t last_relay_launches = 0;
   uint64_t last_relay_parks = 0, last_relay_waiters = 0;
-  unsigned relay_resident_blocks[2][4][3][2] = {}; /* cached occupancy query per kernel instantiation: [sky_filter][log2 supersample][kind][fast] */
+  unsigned relay_resident_blocks[2][2][4][3][2] = {}; /* cached occupancy query per kernel instantiation: [projection != 0][sky_filter][log2 supersample][kind][fast] */
   int relay_resident_threads = 0;                                  /* ... valid for this workgroup size */
   int block_threads = 0; /* workgroup size of the static / relay kernels: 64, 128 or 256; 0 = automatic */
   Event ev2;
@@ -103,6 +103,8 @@ struct curvis_ctx {
                                kernels' epilogues average them (kernels_epilogue.h resolve_store); frames stay res_x x res_y */
   int sky_filter = 0;       /* 0: a ray takes the nearest sky texel (the reference); 1: the bilinear blend of the four around its
                                direction, defined in include/curvis_hip.h (cv_device.h sky_bilinear_taps / sky_bilinear_blend) */
+  int projection = 0;       /* 0: the reference's perspective camera; 1: equirectangular; 2: equidistant fisheye -- pixel -> camera-space
+                               vector, defined in include/curvis_hip.h (cv_device.h camera_pixel_vector) */
   int sampling_speculation = -1; /* efficient renderer: depth of the speculative subtree evaluated below every
                                     refined interval (0 = one launch per refinement round, no speculation;
                                     -1 = automatic: 10 for one or two frames, 6 for three to five, 4 for larger batches;
@@ -182,22 +184,24 @@ template <typename F>
 auto with_flag(bool flag, F &&f) {
   return flag ? f(std::true_type{}) : f(std::false_type{});
 }
-/* The whole shape of a render launch -- metric kind, step flavour, supersampling factor, sky filter -- as ONE type:
- * with_launch_shape(kind, fast, ss, filter, [&](auto S) { using T = decltype(S); ... T::KIND, T::FAST, T::SS, T::FILTER ... }) calls the
- * lambda once.  ss is 1, 2, 4 or 8 and filter 0 or 1: the writers of the options "supersample" and "sky_filter" admit nothing else. */
-template <int KIND_, bool FAST_, int SS_, int FILTER_>
+/* The whole shape of a render launch -- metric kind, step flavour, supersampling factor, sky filter, projection -- as ONE type:
+ * with_launch_shape(kind, fast, ss, filter, projection, [&](auto S) { using T = decltype(S); ... T::KIND, T::FAST, T::SS, T::FILTER,
+ * T::PROJ ... }) calls the lambda once.  ss is 1, 2, 4 or 8 and filter 0 or 1: the writers of the options "supersample" and
+ * "sky_filter" admit nothing else.  PROJ is 1 for every projection but the perspective one: which of them is a kernel argument. */
+template <int KIND_, bool FAST_, int SS_, int FILTER_, int PROJ_>
 struct LaunchShape {
-  static constexpr int KIND = KIND_, SS = SS_, FILTER = FILTER_;
+  static constexpr int KIND = KIND_, SS = SS_, FILTER = FILTER_, PROJ = PROJ_;
   static constexpr bool FAST = FAST_;
 };
 template <typename F>
-auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, F &&f) {
+auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, uint32_t projection, F &&f) {
   return with_kind(kind, [&](auto K) {
     return with_flag(fast, [&](auto A) {
       auto with_ss = [&](auto N) {
         constexpr int KIND = decltype(K)::value, SS = decltype(N)::value;
         constexpr bool FAST = decltype(A)::value;
-        return filter ? f(LaunchShape<KIND, FAST, SS, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0>{});
+        if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1>{});
+        return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0>{});
       };
       switch (ss) {
         case 2: return with_ss(std::integral_constant<int, 2>{});
@@ -212,15 +216,16 @@ inline unsigned supersample_log2(uint32_t ss) { return ss == 8 ? 3u : ss == 4 ? 
 
 /* the filter indexes the virtual sky of 256 w x 256 h texels with 32-bit numbers */
 constexpr uint32_t kSkyFilterMaxSide = 1u << 23;
-/* What the options "supersample" and "sky_filter" make of a render call, for all three renderers: the factor, the filter, and
+/* What the options "supersample", "sky_filter" and "projection" make of a render call, for all three renderers: the factor, the
+ * filter, the projection, and
  * -- ss > 1 -- the cameras of the call over the ss times finer grid: the same sensor at ss times the resolution (pixel (ss x, ss y)
  * of it is pixel (x, y) of the original, cv_device.h ray_init). */
 struct CallShape {
-  uint32_t ss = 1, filter = 0;
+  uint32_t ss = 1, filter = 0, projection = 0;
   std::vector<curvis_camera> fine;
 };
 /* cams: the caller's n_frames cameras on entry, those the kernels run over on return (s.fine with ss > 1).  With the filter on, both
- * skies must be small enough for it; too_large is the renderer's message for a fine resolution that no longer fits 32 bits. */
+ * skies must be small enough for it; a fisheye whose image corner lies beyond the angle pi from the axis is refused; too_large is the renderer's message for a fine resolution that no longer fits 32 bits. */
 int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_frames, const char *too_large, CallShape &s) {
   s.ss = (uint32_t)ctx->supersample;
   s.filter = (uint32_t)ctx->sky_filter;
@@ -228,6 +233,13 @@ int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_f
     for (const auto &sky : ctx->sky)
       if (sky.texels && (sky.w > kSkyFilterMaxSide || sky.h > kSkyFilterMaxSide))
         return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: a sky of more than 2^23 texels per side (256 times its size must fit 32 bits)");
+  s.projection = (uint32_t)ctx->projection;
+  if (s.projection == (uint32_t)cvk::PROJ_FISHEYE)
+    for (uint32_t f = 0; f < n_frames; ++f) {
+      const curvis_camera &c = cams[f];
+      if (!(0.5 * std::sqrt(c.sensor_w * c.sensor_w + c.sensor_h * c.sensor_h) / c.focal <= CV_PI))
+        return fail(ctx, CURVIS_E_INVALID, "projection = 2 (fisheye): half the sensor's diagonal over the focal length exceeds pi");
+    }
   if (s.ss <= 1u) return CURVIS_OK;
   s.fine.assign(cams, cams + n_frames);
   for (curvis_camera &c : s.fine) {
@@ -398,9 +410,9 @@ unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
 }
 
 /* grid = fresh workgroups + relay workgroups; see geodesic_relay */
-template <int KIND, bool FAST, int SS, int FILTER>
+template <int KIND, bool FAST, int SS, int FILTER, int PROJ>
 int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
-  void (*const kernel)(const IntegrateParams, const RelayArgs) = geodesic_relay<KIND, FAST, SS, FILTER>;
+  void (*const kernel)(const IntegrateParams, const RelayArgs) = geodesic_relay<KIND, FAST, SS, FILTER, PROJ>;
   const size_t bytes = sizeof(RelayQueue) + sizeof(unsigned) * kRelayRing;
   if (int rc = ctx->d_rq.reserve(ctx, bytes)) return rc;
   RelayArgs A;
@@ -427,7 +439,7 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
     std::memset(ctx->relay_resident_blocks, 0, sizeof ctx->relay_resident_blocks);
     ctx->relay_resident_threads = (int)bt;
   }
-  unsigned &cached = ctx->relay_resident_blocks[FILTER][supersample_log2(SS)][KIND][FAST ? 1 : 0];
+  unsigned &cached = ctx->relay_resident_blocks[PROJ][FILTER][supersample_log2(SS)][KIND][FAST ? 1 : 0];
   if (cached == 0) {
     int per_cu = 0;
     HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)bt, 0));
@@ -447,14 +459,15 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
 }
 
 /* One launch of the integrator.  relay: 0 no, 1 the relay kernel, 2 its relay-only re-launch.  The unfused static kernel and the
- * persistent one exist for SS = 1, FILTER = 0 only (their static_asserts): render_impl refuses the call shapes that would need more. */
-template <int KIND, bool PHI, bool FAST, int SS, int FILTER>
+ * persistent one exist for SS = 1, FILTER = 0, PROJ = 0 only (their static_asserts): render_impl refuses the call shapes that would need
+ * more. */
+template <int KIND, bool PHI, bool FAST, int SS, int FILTER, int PROJ>
 int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int relay) {
-  if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER>(ctx, P, relay == 2);
+  if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, P, relay == 2);
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const dim3 grid((unsigned)((P.total_rays + bt - 1ull) / bt));
   bool staged = false; /* launched a kernel that leaves the shading to shade_kernel */
-  if constexpr (SS == 1 && FILTER == 0) {
+  if constexpr (SS == 1 && FILTER == 0 && PROJ == 0) {
     if (ctx->variant == 0) {
       int per_cu = ctx->blocks_per_cu;
       if (per_cu <= 0) {
@@ -472,19 +485,19 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int 
       staged = true;
     }
   }
-  if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER>), grid, dim3(bt), 0, ctx->stream, P);
+  if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ>), grid, dim3(bt), 0, ctx->stream, P);
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
 
-/* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled and never filtered */
+/* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled, never filtered and always in perspective */
 int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P, uint32_t ss,
                          uint32_t filter) {
-  return with_launch_shape(kind, fast, ss, filter, [&](auto S) {
+  return with_launch_shape(kind, fast, ss, filter, (uint32_t)P.projection, [&](auto S) {
     using T = decltype(S);
-    if constexpr (T::SS == 1 && T::FILTER == 0)
-      if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0>(ctx, P, false, 0);
-    return launch_integrate<T::KIND, false, T::FAST, T::SS, T::FILTER>(ctx, P, fused, relay);
+    if constexpr (T::SS == 1 && T::FILTER == 0 && T::PROJ == 0)
+      if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0, 0>(ctx, P, false, 0);
+    return launch_integrate<T::KIND, false, T::FAST, T::SS, T::FILTER, T::PROJ>(ctx, P, fused, relay);
   });
 }
 
@@ -529,6 +542,7 @@ struct BruteCall {
   uint32_t ss;                   /* supersampling factor.  With ss > 1 the cameras, the band, W and H are those of the ss times finer
                                     RAY grid (what the kernels run over); npix and fb_bytes are always those of the frames written */
   uint32_t filter;               /* option "sky_filter" for this call */
+  uint32_t projection;           /* option "projection" for this call */
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
   size_t npix = 0, fb_bytes = 0;
 };
@@ -612,6 +626,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   P.fb = ctx->d_fb + (size_t)f0 * c.npix * 3;
   P.refill_threshold = ctx->refill_threshold < 1 ? 1 : (ctx->refill_threshold > 64 ? 64 : ctx->refill_threshold);
   P.fast_ok = cvk::metric_fast_ok(c.metric->kind, MP, c.max_radius) ? 1 : 0;
+  P.projection = (int)c.projection;
   /* diagnostics only (CURVIS_TRACE_FILE): per-wave records of this launch, binary u64 x 4 per wave */
   DeviceBuffer<unsigned long long> trace;
   const char *trace_file = getenv("CURVIS_TRACE_FILE");
@@ -739,9 +754,9 @@ struct LastRenderStats {
  * rendered again (kRenderAgain): the caller gets the static kernel's frame.  Called after a relay render, d_fb holding its frames. */
 int relay_seat_belt(curvis_ctx *ctx, const BruteCall &c) {
   /* everything that shapes the hand-over pattern: size of the ray grid and frame count, metric, step flavour, supersampling
-   * factor and sky filter (other epilogues), the band, the step cap, the segment length and hop limit in force */
+   * factor and sky filter (other epilogues), the projection (other rays), the band, the step cap, the segment length and hop limit in force */
   const std::array<uint32_t, 9> shape = {c.W, c.H, c.n_frames, (uint32_t)c.metric->kind,
-                                         (uint32_t)(ctx->fast_math != 0 ? 1 : 0) | (c.ss << 8) | (c.filter << 16),
+                                         (uint32_t)(ctx->fast_math != 0 ? 1 : 0) | (c.ss << 8) | (c.filter << 16) | (c.projection << 24),
                                          c.row_begin, c.row_count, c.max_iter,
                                          (uint32_t)ctx->relay_segment * 256u + (uint32_t)std::max(0, ctx->relay_max_hops)};
   bool auto_check = false;
@@ -895,27 +910,31 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
 int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
-  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u};
-  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter)) return render_rays(ctx, c);
-  /* only the fused epilogues hold the filtered lookup and the tile-local resolve: three call shapes are refused, under the name of
-   * the filter when it is on, of the supersampling otherwise */
-  const bool f = ctx->sky_filter != 0;
+  BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u, 0u};
+  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->projection)) return render_rays(ctx, c);
+  /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under
+   * the name of the projection when it is on, else of the filter when that is on, of the supersampling otherwise */
+  const bool f = ctx->sky_filter != 0, p = ctx->projection != 0;
   const struct {
     bool refused;
-    const char *filter, *supersample;
+    const char *projection, *filter, *supersample;
   } shapes[3] = {
-      {dbg_out != nullptr, "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)",
+      {dbg_out != nullptr, "projection != 0: the debug dump replays the perspective camera (set projection = 0)",
+       "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)",
        "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)"},
-      {ctx->variant == 0, "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
+      {ctx->variant == 0, "projection != 0: variant = 0 (the persistent kernel) has the perspective camera only",
+       "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
        "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve"},
-      {ctx->fuse_shade == 0, "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
+      {ctx->fuse_shade == 0, "projection != 0: fuse_shade = 0 (the unfused static kernel) has the perspective camera only",
+       "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
        "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve"}};
   for (const auto &s : shapes)
-    if (s.refused) return fail(ctx, CURVIS_E_INVALID, f ? s.filter : s.supersample);
+    if (s.refused) return fail(ctx, CURVIS_E_INVALID, p ? s.projection : f ? s.filter : s.supersample);
   CallShape shape;
   if (int rc = prepare_call_shape(ctx, c.cams, n_frames, "frame or batch too large", shape)) return rc;
   c.ss = shape.ss;
   c.filter = shape.filter;
+  c.projection = shape.projection;
   if ((uint64_t)row_begin * c.ss > 0xFFFFFFFFull || (uint64_t)row_count * c.ss > 0xFFFFFFFFull)
     return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
   c.row_begin *= c.ss;

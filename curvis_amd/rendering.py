@@ -132,14 +132,18 @@ class ImageRenderingSystem:
     extension of the name is replaced, PathBuf::with_extension).  mode="brute" renders with the per-pixel
     integrator instead (not in the reference's ImageRenderingSystem); supersample=N (1, 2, 4 or 8; not in the reference either)
     traces N x N rays per pixel and averages them on the device; sky_filter="bilinear" (not in the reference; "nearest" is its
-    lookup) blends the four sky texels around every ray's direction."""
+    lookup) blends the four sky texels around every ray's direction; projection="equirectangular" or "fisheye" (not in the reference;
+    "perspective" is its camera) renders a 360-degree or a dome frame (library option "projection")."""
 
-    def __init__(self, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest"):
+    def __init__(self, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
+                 projection="perspective"):
         from .images import load_image_as_spherical_image
-        from .systems import RelativisticSystem, check_sky_filter, check_supersample
+        from .systems import RelativisticSystem, check_projection, check_sky_filter, check_supersample
         self.supersample = check_supersample(supersample)
         check_sky_filter(sky_filter)
         self.sky_filter = sky_filter
+        check_projection(projection)
+        self.projection = projection
         st = self.image_rendering_settings = image_rendering_settings
         self.mode = mode
         image_1 = load_image_as_spherical_image(st.path_to_background_image_1)
@@ -149,9 +153,11 @@ class ImageRenderingSystem:
         self.relativistic_system = RelativisticSystem(metric, image_1, image_2, camera, context=context)
 
     @classmethod
-    def new(cls, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest"):
+    def new(cls, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
+            projection="perspective"):
         """ImageRenderingSystem::new(metric, image_rendering_settings) (src/rendering.rs:33-70)"""
-        return cls(metric, image_rendering_settings, context=context, mode=mode, supersample=supersample, sky_filter=sky_filter)
+        return cls(metric, image_rendering_settings, context=context, mode=mode, supersample=supersample, sky_filter=sky_filter,
+                   projection=projection)
 
     def render(self):
         import os
@@ -165,12 +171,13 @@ class ImageRenderingSystem:
                 raise RuntimeError("Could not create video output folder %r due to error: %s" % (folder, err))
         if self.mode == "brute":
             image = self.relativistic_system.render_image(st.max_iterations_propagation, st.escape_radius, st.ray_integration_step,
-                                                          supersample=self.supersample, sky_filter=self.sky_filter)
+                                                          supersample=self.supersample, sky_filter=self.sky_filter,
+                                                          projection=self.projection)
         else:
             image = self.relativistic_system.render_image_efficient(
                 st.max_iterations_propagation, st.escape_radius, st.ray_integration_step, st.alphas_num,
                 st.max_iterations_sampling, st.sampling_convergence_threshold_1, st.sampling_convergence_threshold_2,
-                supersample=self.supersample, sky_filter=self.sky_filter)
+                supersample=self.supersample, sky_filter=self.sky_filter, projection=self.projection)
         path_of_image = os.path.join(folder, os.path.splitext(st.output_image_name)[0] + ".png")
         save_image(path_of_image, image)
         return path_of_image
@@ -197,18 +204,21 @@ class VideoRenderingSystem:
     integrator (RelativisticSystem::render_image, src/systems.rs:307-330), the path bench.py measures.  supersample=N (1, 2, 4 or
     8; not in the reference) traces N x N rays per pixel of `resolution` and averages them on the device: frames, PNG streams
     and downloads keep `resolution`, the per-frame statistics count the N x N times as many rays.  sky_filter="bilinear" (not in
-    the reference; "nearest" is its lookup) blends the four sky texels around every ray's direction."""
+    the reference; "nearest" is its lookup) blends the four sky texels around every ray's direction.  projection="equirectangular" or
+    "fisheye" (not in the reference; "perspective" is its camera): library option "projection" on every frame."""
 
     def __init__(self, metric, context, interpolator, frame_rate, resolution, camera_diagonal, camera_focal_length,
                  escape_radius, max_iterations_propagation, ray_integration_step, rank=0, world_size=1, batch=8,
                  mode="efficient", sampling_initial_nums=100, sampling_convergence_threshold_1=1e-5, supersample=1,
-                 sky_filter="nearest"):
-        from .systems import check_sky_filter, check_supersample
+                 sky_filter="nearest", projection="perspective"):
+        from .systems import check_projection, check_sky_filter, check_supersample
         if mode not in ("efficient", "brute"):
             raise ValueError("mode must be 'efficient' or 'brute'")
         self.supersample = check_supersample(supersample)
         self._sky_filter = check_sky_filter(sky_filter)
         self.sky_filter = sky_filter
+        self._projection = check_projection(projection)
+        self.projection = projection
         self.metric = metric
         self.context = context
         self.interpolator = interpolator
@@ -226,15 +236,16 @@ class VideoRenderingSystem:
 
     @classmethod
     def new(cls, metric, video_rendering_settings, context=None, rank=0, world_size=1, batch=8, mode="efficient", supersample=1,
-            sky_filter="nearest"):
+            sky_filter="nearest", projection="perspective"):
         """VideoRenderingSystem::new(metric, video_rendering_settings) (src/rendering.rs:188-221): loads the two
         backgrounds into the context's HBM and the camera path into an Interpolator.  The reference passes
         `alphas_num` and `max_iterations_sampling` separately and `sampling_convergence_threshold_1` twice (:299-307);
         so does this (threshold_2 of the settings is never read, as there)."""
         from .images import load_image_as_spherical_image
-        from .systems import check_sky_filter, check_supersample, default_context
+        from .systems import check_projection, check_sky_filter, check_supersample, default_context
         check_supersample(supersample)  # before the context and the files are touched
         check_sky_filter(sky_filter)
+        check_projection(projection)
         st = video_rendering_settings
         context = context or default_context()
         context.set_sky(0, load_image_as_spherical_image(st.filepath_to_background_image_1))
@@ -244,7 +255,7 @@ class VideoRenderingSystem:
                    st.max_iterations_propagation, st.ray_integration_step, rank=rank, world_size=world_size, batch=batch,
                    mode=mode, sampling_initial_nums=st.alphas_num,
                    sampling_convergence_threshold_1=st.sampling_convergence_threshold_1, supersample=supersample,
-                   sky_filter=sky_filter)
+                   sky_filter=sky_filter, projection=projection)
         self.max_iterations_sampling = int(st.max_iterations_sampling)
         self.video_rendering_settings = st
         return self
@@ -299,9 +310,10 @@ class VideoRenderingSystem:
                       self.camera_diagonal, self.resolution[0], self.resolution[1])
 
     def _render_batch(self, cams, download):
-        if getattr(self, "supersample", 1) != 1 or getattr(self, "_sky_filter", 0) != 0:
+        if getattr(self, "supersample", 1) != 1 or getattr(self, "_sky_filter", 0) != 0 or getattr(self, "_projection", 0) != 0:
             from .systems import _Supersampled
-            with _Supersampled(self.context, getattr(self, "supersample", 1), getattr(self, "_sky_filter", 0)):
+            with _Supersampled(self.context, getattr(self, "supersample", 1), getattr(self, "_sky_filter", 0),
+                               getattr(self, "_projection", 0)):
                 return self._render_batch_as_set(cams, download)
         return self._render_batch_as_set(cams, download)
 

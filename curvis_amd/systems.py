@@ -193,16 +193,19 @@ class Camera:
     def rotation_matrix(self):
         return np.array(self._c.rot[:]).reshape(3, 3)
 
-    def outward_vector_on_camera_space(self, camera_pixel_x, camera_pixel_y):
-        """src/cameras.rs:150-164: unit vector through pixel (x, y) in camera space (x forward, y left, z up)"""
+    def outward_vector_on_camera_space(self, camera_pixel_x, camera_pixel_y, projection="perspective"):
+        """src/cameras.rs:150-164: unit vector through pixel (x, y) in camera space (x forward, y left, z up); projection
+        "equirectangular" or "fisheye" (not in the reference): the vector library option "projection" gives the pixel"""
         out = np.zeros(3)
-        check(lib().curvis_camera_outward_vector(C.byref(self._c), int(camera_pixel_x), int(camera_pixel_y), dptr(out), None))
+        check(lib().curvis_camera_outward_vector_projected(C.byref(self._c), check_projection(projection), int(camera_pixel_x),
+                                                           int(camera_pixel_y), dptr(out), None))
         return out
 
-    def outward_vector_on_world_space_from_x_y(self, camera_pixel_x, camera_pixel_y):
+    def outward_vector_on_world_space_from_x_y(self, camera_pixel_x, camera_pixel_y, projection="perspective"):
         """src/cameras.rs:169-172: the same vector in the tangent space of the camera's position"""
         out = np.zeros(3)
-        check(lib().curvis_camera_outward_vector(C.byref(self._c), int(camera_pixel_x), int(camera_pixel_y), None, dptr(out)))
+        check(lib().curvis_camera_outward_vector_projected(C.byref(self._c), check_projection(projection), int(camera_pixel_x),
+                                                           int(camera_pixel_y), None, dptr(out)))
         return out
 
     @property
@@ -763,12 +766,23 @@ def check_sky_filter(sky_filter):
     return SKY_FILTERS.index(sky_filter)
 
 
-class _Supersampled:
-    """the context's "supersample" option set to `factor` -- and "sky_filter" to `sky_filter` (0 or 1) -- for the duration of a render
-    call, then put back"""
+PROJECTIONS = ("perspective", "equirectangular", "fisheye")  # the values of library option "projection", 0, 1 and 2
 
-    def __init__(self, context, factor, sky_filter=0):
-        self.context, self.want = context, (("supersample", factor), ("sky_filter", sky_filter))
+
+def check_projection(projection):
+    """the projection as the library option's value, or ValueError: "perspective" (0, the reference's), "equirectangular" (1) or
+    "fisheye" (2)"""
+    if not isinstance(projection, str) or projection not in PROJECTIONS:
+        raise ValueError("projection must be 'perspective', 'equirectangular' or 'fisheye'")
+    return PROJECTIONS.index(projection)
+
+
+class _Supersampled:
+    """the context's "supersample" option set to `factor` -- and "sky_filter" to `sky_filter` (0 or 1), "projection" to `projection`
+    (0, 1 or 2) -- for the duration of a render call, then put back"""
+
+    def __init__(self, context, factor, sky_filter=0, projection=0):
+        self.context, self.want = context, (("supersample", factor), ("sky_filter", sky_filter), ("projection", projection))
 
     def __enter__(self):
         self.before = [self.context.get_option(key) for key, _ in self.want]
@@ -786,7 +800,9 @@ class _Supersampled:
 class RelativisticSystem:
     """RelativisticSystem<M> (src/systems.rs:68-73).  The three renderers take supersample=N (1, 2, 4 or 8; not in the
     reference): N x N rays per pixel, averaged on the device into the camera's resolution; and sky_filter="nearest" (the
-    reference's lookup) or "bilinear" (not in the reference: the four texels around a ray's direction, blended on the device)."""
+    reference's lookup) or "bilinear" (not in the reference: the four texels around a ray's direction, blended on the device); and
+    projection="perspective" (the reference's camera), "equirectangular" or "fisheye" (not in the reference: library option
+    "projection")."""
 
     def __init__(self, metric, background_positive, background_negative, camera, context=None):
         self.metric = metric
@@ -803,34 +819,34 @@ class RelativisticSystem:
         if ctx._sky_objs[1] is not self.background_negative:
             ctx.set_sky(1, self.background_negative)
 
-    def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest"):
+    def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective"):
         """The per-pixel renderer; returns an HxWx3 uint8 array (DynamicImage::ImageRgb8)."""
-        factor, filt = check_supersample(supersample), check_sky_filter(sky_filter)
+        factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt):
+        with _Supersampled(self.context, factor, filt, proj):
             rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
         self.last_stats = st
         return rgb
 
     def render_image_efficient(self, max_iterations_propagation, max_radius, delta, alpha_nums,
                                max_iterations_sampling, sampling_convergence_threshold_1,
-                               sampling_convergence_threshold_2, supersample=1, sky_filter="nearest"):
+                               sampling_convergence_threshold_2, supersample=1, sky_filter="nearest", projection="perspective"):
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
-        factor, filt = check_supersample(supersample), check_sky_filter(sky_filter)
+        factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt):
+        with _Supersampled(self.context, factor, filt, proj):
             rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
                                                     alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
                                                     sampling_convergence_threshold_2)
         self.last_stats = st
         return rgb
 
-    def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest"):
+    def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective"):
         """NOT in the reference: the image render_image_efficient approximates, with compute_escape_angle evaluated
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
-        factor, filt = check_supersample(supersample), check_sky_filter(sky_filter)
+        factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt):
+        with _Supersampled(self.context, factor, filt, proj):
             rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
         self.last_stats = st
         return rgb

@@ -180,6 +180,12 @@ int curvis_render_brute(curvis_ctx *ctx, const curvis_metric *metric, const curv
  * outward_vector_on_world_space_from_x_y (:169-172, the former rotated by camera_to_world); either output may be NULL. */
 int curvis_camera_outward_vector(const curvis_camera *camera, uint32_t px, uint32_t py, double camera_space[3],
                                  double world_space[3]);
+/* The same for option "projection" (defined with the options below): the unit camera-space vector of pixel (px, py) under
+ * projection 0, 1 or 2 -- the un-normalised vec of the definition through the reference's normalize -- and its rotation into world
+ * space.  Projection 0 is curvis_camera_outward_vector bit for bit; any other value than 0, 1, 2 is CURVIS_E_INVALID.  The fisheye
+ * range check is made by the render calls, not here. */
+int curvis_camera_outward_vector_projected(const curvis_camera *camera, int32_t projection, uint32_t px, uint32_t py,
+                                           double camera_space[3], double world_space[3]);
 /* DiagonalSphericalMetric::relativistic_vector_to_direction (src/metrics.rs:339-349 with to_contravariant :190-203):
  * covariant momentum at `position` -> tangent-space direction (not normalised; z uses frame_field_22, as the
  * reference does). */
@@ -409,6 +415,28 @@ int curvis_ctx_download_wait(curvis_ctx *ctx);
  * the N x N box average is taken over the filtered colours.  A render call with the filter on and a sky wider or taller than 2^23
  * texels fails with CURVIS_E_INVALID (256 w must stay a u32); so do, as under supersampling, curvis_render_brute_debug,
  * "variant" = 0 and "fuse_shade" = 0.  Sampler prefetch, PNG front end, downloads, row bands and batches are untouched),
+ * "projection" (0 = perspective, the default and the reference's mapping bit for bit, 1 = equirectangular, 2 = equidistant fisheye;
+ * anything else is refused with CURVIS_E_INVALID and the old value stays.  It replaces only the three expressions that form the
+ * un-normalised camera-space vector vec = (x, y, z) of a pixel (camera axes as in the reference: x forward, y left, z up); everything
+ * behind it is the reference's sequence unchanged -- vec.normalize() with norm sqrt((x x + y y) + z z) and three divisions, the camera
+ * rotation, new_photon's second normalisation, the Euler loop and the lookup; in the efficient and direct renderers rot_bg, the
+ * cross product and acos.  Every operation is an individually rounded FP64 one in the order written, no contraction; sin and cos
+ * are cv_math.h's table-driven ones, pi is CV_PI and 2 pi is 2.0 * CV_PI.  For projection != 0 a pixel is sampled at its centre:
+ *   u = (double)(2 px + 1) / (double)(2 res_x),  v = (double)(2 py + 1) / (double)(2 res_y)
+ * each ONE correctly rounded quotient of two exactly representable integers (the efficient pixel kernel forms it from the call's
+ * shared reciprocals and delivers that quotient).
+ *   1, equirectangular (focal, sensor_w, sensor_h are not read):
+ *      psi = (0.5 - u) * (2 pi),  th = v * pi,  vec = (sin(th) cos(psi), sin(th) sin(psi), cos(th))
+ *      -- the image centre looks along `forward`, the left and right edges meet looking backward, row 0 is nearest `up`.
+ *   2, fisheye (image radius = focal * angle from the axis, on the camera's own sensor and focal length):
+ *      ys = -sensor_w * (u - 0.5),  zs = sensor_h * (0.5 - v),  rho = sqrt(ys ys + zs zs),  b = rho / focal,
+ *      vec = (cos(b), sin(b) (ys / rho), sin(b) (zs / rho)), and vec = (1, 0, 0) when rho == 0 (the centre pixel of an odd x odd
+ *      frame).  A render call fails with CURVIS_E_INVALID when 0.5 sqrt(sensor_w^2 + sensor_h^2) / focal > pi.
+ * With "supersample" = N, px, py, res_x, res_y are the fine grid's and the box average is that of the frame the same renderer
+ * gives at N res_x x N res_y; "sky_filter" acts on the final direction and is untouched; counters are those of the rays actually
+ * traced.  Refused with CURVIS_E_INVALID while projection != 0, as under the two options above: curvis_render_brute_debug,
+ * "variant" = 0 and "fuse_shade" = 0 (only the fused kernels have the projections).  The relay seat belt checks a projected launch
+ * shape on its own),
  * "max_store_bytes" (ray-store budget that bounds the frames per launch of a batch),
  * "sampling_speculation" (efficient renderer: depth of the speculative dyadic subtree evaluated below every
  * refined interval; 0 = one launch per refinement round; default -1 = automatic, 10 for one or two frames, 6 for three to five and 4
