@@ -560,6 +560,11 @@ int curvis_update_relativistic_object(const curvis_metric *metric, double x[4], 
   return CURVIS_OK;
 }
 
+int curvis_step_delta(double delta, int64_t step_scale, double l, double *out) {
+  static_assert(cvk::kStepScaleMax == (long long)CURVIS_STEP_SCALE_MAX, "one bound");
+  return cvk::step_delta_of_scale(delta, (long long)step_scale, l, out) ? CURVIS_OK : CURVIS_E_INVALID;
+}
+
 int curvis_sky_texel_index(uint32_t w, uint32_t h, const double inv_rot[9], const double v[3], uint32_t *x, uint32_t *y) {
   if (!v || !x || !y || w == 0 || h == 0) return CURVIS_E_INVALID;
   cvk::SkyParams S;
@@ -948,6 +953,12 @@ const OptionEntry kOptions[] = {
      [](curvis_ctx *c, int64_t v) -> int {
        if (v < 0 || v > 2) return fail(c, CURVIS_E_INVALID, "projection must be 0 (perspective), 1 (equirectangular) or 2 (fisheye)");
        c->projection = (int)v;
+       return CURVIS_OK;
+     }},
+    {"step_scale", OPT_READ(c->step_scale),
+     [](curvis_ctx *c, int64_t v) -> int {
+       if (v < 0 || v > (int64_t)CURVIS_STEP_SCALE_MAX) return fail(c, CURVIS_E_INVALID, "step_scale must be 0 (off) or L0 x 256 in 1 .. 2^20");
+       c->step_scale = v;
        return CURVIS_OK;
      }},
     OPT_RW(device_sampler, int),

@@ -147,6 +147,32 @@ CV_HD void ray_step(const MetricParams &M, Ray &q, double delta) {
   ray_step_core<KIND, PHI>(M, q, delta, s, c);
 }
 
+/* Option "step_scale" (include/curvis_hip.h): the step of a ray whose radial coordinate BEFORE the step is l.  kappa = RN(delta / L0)
+ * is formed once per call on the host; a = RN(|l| kappa), and the step is a where a > delta, else delta (a NaN l fails the compare and
+ * takes delta).  One text for host and device: every integrating loop that honours the option calls it, and curvis_step_delta is
+ * its host accessor.  Two FP64 instructions per step and lane: a multiply with an |l| source modifier and a maximum. */
+CV_HD double step_kappa(double delta, long long step_scale) { return delta / ((double)step_scale / 256.0); }
+CV_HD double step_delta(double delta, double kappa, double l) {
+  const double a = CV_FABS(l) * kappa;
+  /* (a > delta) ? a : delta, written as the IEEE maximum: the same value in every case -- a > delta gives a, a <= delta gives delta, and
+   * a NaN a gives the operand that is a number, delta (delta > 0 is checked on the host, so it is never the NaN) -- and ONE v_max_f64
+   * on the device where the compare-select is a v_cmp and two v_cndmask_b32 */
+  return __builtin_fmax(a, delta);
+}
+/* the body of the host accessor curvis_step_delta: kappa as the render calls form it, then step_delta; S = 0 is delta.  false for S
+ * outside [0, 2^20], a null `out`, and S != 0 with !(delta > 0) */
+constexpr long long kStepScaleMax = 1ll << 20;
+CV_HD bool step_delta_of_scale(double delta, long long step_scale, double l, double *out) {
+  if (!out || step_scale < 0 || step_scale > kStepScaleMax) return false;
+  if (step_scale == 0) {
+    *out = delta;
+    return true;
+  }
+  if (!(delta > 0.0)) return false;
+  *out = step_delta(delta, step_kappa(delta, step_scale), l);
+  return true;
+}
+
 /* ------------------------------------------------------------------------------------------------
  * Fast step: the same IEEE results with far fewer instructions.
  *

@@ -18,13 +18,15 @@ struct EfficientCall {
   uint32_t filter = 0; /* option "sky_filter" for this call */
   uint32_t projection = 0; /* option "projection" for this call */
   uint32_t ss = 1; /* supersampling factor: with ss > 1 `cams` are those of the ss times finer pixel grid (render_efficient_impl) */
+  double kappa = 0.0; /* option "step_scale" for this call: RN(delta / L0) ... */
+  bool adapt = false; /* ... and whether it is on: the samplers integrate with step_delta */
 };
 
 /* evaluate compute_escape_angle for a batch on the GPU */
 int eval_escape_batch(curvis_ctx *ctx, const curvis_metric *metric, const cvk::MetricParams &MP,
                       const std::vector<double> &alpha, const std::vector<double> &lcam, uint32_t max_iter,
                       double max_radius, double delta, std::vector<double> &angle, std::vector<double> &space,
-                      std::vector<uint32_t> &steps, std::vector<int> &status, double *ms_acc) {
+                      std::vector<uint32_t> &steps, std::vector<int> &status, double *ms_acc, bool adapt = false, double kappa = 0.0) {
   const size_t n = alpha.size();
   angle.resize(n);
   space.resize(n);
@@ -46,7 +48,7 @@ int eval_escape_batch(curvis_ctx *ctx, const curvis_metric *metric, const cvk::M
   std::memcpy(h_alpha, alpha.data(), n * sizeof(double));
   std::memcpy(h_l, lcam.data(), n * sizeof(double));
   HIP_TRY(ctx, hipMemcpyAsync(d_alpha, h_alpha, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  EscapeAngleParams P;
+  EscapeAngleParamsAdapt P;
   P.metric = MP;
   P.alpha = d_alpha;
   P.l_cam = d_l;
@@ -59,10 +61,19 @@ int eval_escape_batch(curvis_ctx *ctx, const curvis_metric *metric, const cvk::M
   P.max_radius = max_radius;
   P.delta = delta;
   P.fast_ok = cvk::metric_fast_ok(metric->kind, MP, max_radius) ? 1 : 0;
+  P.kappa = kappa;
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   with_kind(metric->kind, [&](auto K) {
     with_flag(ctx->fast_math != 0, [&](auto F) {
-      hipLaunchKernelGGL((escape_angle_kernel<decltype(K)::value, decltype(F)::value>), dim3((P.n + 63u) / 64u), dim3(64), 0, ctx->stream, P);
+      constexpr int KIND = decltype(K)::value;
+      constexpr bool FAST = decltype(F)::value;
+      const dim3 grid((P.n + 63u) / 64u);
+      if constexpr (FAST) /* option "step_scale": the fast step only (step_scale_kappa refuses the other) */
+        if (adapt) {
+          hipLaunchKernelGGL((escape_angle_kernel<KIND, true, 1>), grid, dim3(64), 0, ctx->stream, P);
+          return;
+        }
+      hipLaunchKernelGGL((escape_angle_kernel<KIND, FAST>), grid, dim3(64), 0, ctx->stream, static_cast<const EscapeAngleParams &>(P));
     });
   });
   HIP_TRY(ctx, hipGetLastError());
@@ -149,7 +160,7 @@ int launch_pixel_kernel(curvis_ctx *ctx, EfficientPixelParams Q, uint32_t n_fram
   const unsigned long long tiles = (unsigned long long)((Q.W + 7u) / 8u) * ((Q.H + 7u) / 8u);
   if (ss > 1u && (tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
   const unsigned long long groups = ss > 1u ? (tiles + 3ull) / 4ull : ((unsigned long long)Q.W * Q.H + 255ull) / 256ull;
-  with_launch_shape(0, false, ss, filter, projection, [&](auto S) { /* the metric kind and the step flavour mean nothing to K3 */
+  with_launch_shape(0, false, ss, filter, projection, false, [&](auto S) { /* the metric kind and the step flavour mean nothing to K3 */
     using T = decltype(S);
     const dim3 grid((unsigned)groups, n_frames);
     if constexpr (T::SS > 1) hipLaunchKernelGGL((efficient_pixel_ss_kernel<T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, Q);
@@ -212,6 +223,7 @@ curvis_ctx::SamplerKey make_sampler_key(const curvis_ctx *ctx, const EfficientCa
   k.max_radius = c.max_radius, k.delta = c.delta, k.thr1 = c.thr1, k.thr2 = c.thr2;
   k.fast = ctx->fast_math != 0 ? 1 : 0;
   k.speculate = ctx->sampling_speculation != 0 ? 1 : 0; /* option "sampling_speculation" = 0 switches it off in the kernel too */
+  k.step_scale = c.adapt ? ctx->step_scale : 0; /* a prefetch made under another value is another job: it is not consumed */
   k.l_frame.resize(c.n_frames);
   for (uint32_t f = 0; f < c.n_frames; ++f) k.l_frame[f] = c.cams[f].pos[1];
   return k;
@@ -222,7 +234,7 @@ bool sampler_key_equal(const curvis_ctx::SamplerKey &a, const curvis_ctx::Sample
   if (a.metric.kind != b.metric.kind || !same(a.metric.rho, b.metric.rho) || !same(a.metric.m, b.metric.m) || !same(a.metric.a, b.metric.a))
     return false;
   if (a.n_frames != b.n_frames || a.max_iter != b.max_iter || a.alpha_nums != b.alpha_nums ||
-      a.max_iterations_sampling != b.max_iterations_sampling || a.fast != b.fast || a.speculate != b.speculate)
+      a.max_iterations_sampling != b.max_iterations_sampling || a.fast != b.fast || a.speculate != b.speculate || a.step_scale != b.step_scale)
     return false;
   if (!same(a.max_radius, b.max_radius) || !same(a.delta, b.delta) || !same(a.thr1, b.thr1) || !same(a.thr2, b.thr2)) return false;
   return a.l_frame.size() == b.l_frame.size() &&
@@ -301,7 +313,7 @@ int sampler_submit(curvis_ctx *ctx, unsigned slot, hipStream_t stream, const Eff
   HIP_TRY(ctx, hipMemcpyAsync(S.d, S.h, staged, hipMemcpyHostToDevice, stream));
   HIP_TRY(ctx, hipMemsetAsync(S.d + o_sk, 0xFF, sizeof(unsigned long long) * SS, stream)); /* every key = kSpecEmpty */
   curvis_ctx::SamplerKey key = make_sampler_key(ctx, c);
-  SamplerParams SP;
+  SamplerParamsAdapt SP;
   SP.metric = MP;
   SP.l_cam = (const double *)(S.d + o_l);
   SP.n_jobs = n_jobs;
@@ -333,10 +345,18 @@ int sampler_submit(curvis_ctx *ctx, unsigned slot, hipStream_t stream, const Eff
   SP.spec_steps = (unsigned *)(S.d + o_st);
   SP.spec_status = (int *)(S.d + o_su);
   SP.speculate = key.speculate;
+  SP.kappa = c.kappa;
   HIP_TRY(ctx, hipEventRecord(S.t0, stream));
   with_kind(c.metric->kind, [&](auto K) {
     with_flag(key.fast != 0, [&](auto F) {
-      hipLaunchKernelGGL((sampler_kernel<decltype(K)::value, decltype(F)::value>), dim3(SP.n_jobs), dim3(kSamplerThreads), 0, stream, SP);
+      constexpr int KIND = decltype(K)::value;
+      constexpr bool FAST = decltype(F)::value;
+      if constexpr (FAST) /* option "step_scale": the fast step only */
+        if (c.adapt) {
+          hipLaunchKernelGGL((sampler_kernel<KIND, true, 1>), dim3(SP.n_jobs), dim3(kSamplerThreads), 0, stream, SP);
+          return;
+        }
+      hipLaunchKernelGGL((sampler_kernel<KIND, FAST>), dim3(SP.n_jobs), dim3(kSamplerThreads), 0, stream, static_cast<const SamplerParams &>(SP));
     });
   });
   HIP_TRY(ctx, hipGetLastError());
@@ -353,9 +373,11 @@ int sampler_submit(curvis_ctx *ctx, unsigned slot, hipStream_t stream, const Eff
  * The sampler's cost is latency (a handful of Euler chains on a few compute units), the per-pixel kernel's and the PNG front end's
  * is throughput, and between them a render call leaves the GPU to the host (stream download, hand-over): the next call's sampler
  * fits into all of that.  The call with the same metric, settings and camera radii then waits for the event instead of sampling. */
-int prefetch_efficient_impl(curvis_ctx *ctx, const EfficientCall &c) {
+int prefetch_efficient_impl(curvis_ctx *ctx, const EfficientCall &call) {
   if (!ctx) return CURVIS_E_INVALID;
-  if (!c.metric || !c.cams || c.n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
+  if (!call.metric || !call.cams || call.n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
+  EfficientCall c = call;
+  if (int rc = step_scale_kappa(ctx, c.delta, c.kappa, c.adapt)) return rc; /* option "step_scale": part of what the job is */
   int rc = curvis_metric_validate(c.metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   /* not a case for the device sampler, or (alpha_nums < 3) one that at most runs one round: the render call samples itself */
@@ -700,7 +722,7 @@ int sample_host_paced(curvis_ctx *ctx, const EfficientCall &c, const cvk::Metric
     }
     const auto tp2 = now();
     t_build += secs(tp1, tp2);
-    rc = eval_escape_batch(ctx, c.metric, MP, b_alpha, b_l, c.max_iter, c.max_radius, c.delta, r_angle, r_space, r_steps, r_status, &sample_ms);
+    rc = eval_escape_batch(ctx, c.metric, MP, b_alpha, b_l, c.max_iter, c.max_radius, c.delta, r_angle, r_space, r_steps, r_status, &sample_ms, c.adapt, c.kappa);
     if (rc) return rc;
     const auto tp3 = now();
     t_eval += secs(tp2, tp3);
@@ -858,7 +880,9 @@ int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *r
    * option "projection" != 0: the per-pixel kernel forms other directions; the samplers tabulate the whole sphere as it is */
   EfficientCall c = call;
   CallShape shape;
-  if (int rc = prepare_call_shape(ctx, c.cams, c.n_frames, "frame or batch too large", shape)) return rc;
+  if (int rc = prepare_call_shape(ctx, c.cams, c.n_frames, c.delta, "frame or batch too large", shape)) return rc;
+  c.kappa = shape.kappa;
+  c.adapt = shape.adapt;
   c.ss = shape.ss;
   c.filter = shape.filter;
   c.projection = shape.projection;
@@ -938,9 +962,10 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   /* option "supersample" = N > 1: the camera of the N times finer grid, averaged into res_x x res_y by the kernel's epilogue */
-  DirectParams P;
+  DirectParamsAdapt P;
   CallShape shape;
-  if ((rc = prepare_call_shape(ctx, cam, 1, "frame too large", shape))) return rc;
+  if ((rc = prepare_call_shape(ctx, cam, 1, delta, "frame too large", shape))) return rc;
+  P.kappa = shape.kappa;
   const uint32_t ss = shape.ss, filter = shape.filter;
   P.projection = (int)shape.projection;
   const uint32_t W = cam->res_x, H = cam->res_y;
@@ -975,10 +1000,11 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   P.counters = FC;
   const size_t cnt_words = counter_words(1, FC.slots);
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, shape.projection, [&](auto S) {
+  with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, shape.projection, shape.adapt, [&](auto S) {
     using T = decltype(S);
     const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
-    hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, P);
+    if constexpr (T::ADAPT != 0) hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, 1>), grid, dim3(256), 0, ctx->stream, P);
+    else hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, static_cast<const DirectParams &>(P));
   });
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));

@@ -19,10 +19,12 @@ struct Args {
   int supersample = 1; /* rays per pixel and axis, averaged on the device (library option "supersample"): 1, 2, 4 or 8 */
   int sky_filter = 0; /* sky lookup (library option "sky_filter"): 0 nearest texel, 1 bilinear */
   int projection = 0; /* pixel -> direction (library option "projection"): 0 perspective, 1 equirectangular, 2 fisheye */
+  long long step_scale = 0; /* --step-scale L0 as library option "step_scale" = 256 L0: 0 off, else the Euler step grows as |l| / L0 outside L0 */
 };
 int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
 int g_sky_filter = 0;  /* Args::sky_filter, likewise */
 int g_projection = 0;  /* Args::projection, likewise */
+long long g_step_scale = 0; /* Args::step_scale, likewise */
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(code);
@@ -37,7 +39,7 @@ void usage() {
       "  extensions: [--mode efficient|brute|direct] [--device N] [--devices N] [--batch B] [--stats FILE]\n"
       "              [--sky-broadcast rccl|upload] [--writers T] [--resume] [--png-level -1..9] [--gpu-png auto|on|off]\n"
       "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n"
-      "              [--projection perspective|equirectangular|fisheye]\n");
+      "              [--projection perspective|equirectangular|fisheye] [--step-scale L0]\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -96,6 +98,18 @@ Args parse_args(int argc, char **argv) {
       if (val != "perspective" && val != "equirectangular" && val != "fisheye")
         die("error: --projection must be perspective, equirectangular or fisheye", 2);
       a.projection = g_projection = val == "fisheye" ? 2 : val == "equirectangular" ? 1 : 0;
+    }
+    else if (key == "--step-scale") { /* a decimal number L0, a multiple of 1/256 in [0, 4096]: 256 L0 is the library's integer */
+      take(val);
+      char *end = nullptr;
+      /* digits, one point, an optional exponent: no sign, no blank, no hexadecimal or named value of strtod's */
+      const bool decimal = !val.empty() && val.find_first_not_of("0123456789.eE+-") == std::string::npos &&
+                           ((val[0] >= '0' && val[0] <= '9') || val[0] == '.');
+      const double l0 = decimal ? std::strtod(val.c_str(), &end) : -1.0;
+      const double scaled = l0 * 256.0;
+      if (!decimal || *end != '\0' || !(scaled >= 0.0) || scaled > 1048576.0 || scaled != (double)(long long)scaled)
+        die("error: --step-scale must be 0 or a multiple of 1/256 up to 4096", 2);
+      a.step_scale = g_step_scale = (long long)scaled;
     }
     else if (key == "-h" || key == "--help") { usage(); std::exit(0); }
     else if (!s.empty() && s[0] == '-') die("error: unexpected argument '" + s + "' found", 2);
@@ -246,6 +260,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
   if (g_supersample != 1) check(curvis_ctx_set_option(ctx, "supersample", g_supersample), ctx, what);
   if (g_sky_filter != 0) check(curvis_ctx_set_option(ctx, "sky_filter", g_sky_filter), ctx, what);
   if (g_projection != 0) check(curvis_ctx_set_option(ctx, "projection", g_projection), ctx, what);
+  if (g_step_scale != 0) check(curvis_ctx_set_option(ctx, "step_scale", g_step_scale), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {

@@ -20,13 +20,19 @@ struct EscapeAngleParams {
   double max_radius, delta;
   int fast_ok;
 };
+/* the ADAPT instantiation's argument (option "step_scale", cv_device.h step_delta): kappa appended; the other kernels' arguments stay
+ * where they are, the hidden ones behind the struct included */
+struct EscapeAngleParamsAdapt : EscapeAngleParams {
+  double kappa;
+};
 
 /* compute_escape_angle (src/systems.rs:203-261) for ONE alpha on one lane: photon at (0, l, pi/2, 0) with tangent direction
  * (cos a, 0, sin a), Euler loop WITH phi, world direction, angle.  Every lane of the wave that is active here must have entered
- * together (the step counter is wave-uniform). */
-template <int KIND, bool FAST>
+ * together (the step counter is wave-uniform).  ADAPT: option "step_scale" != 0, every step takes step_delta(delta, kappa, l). */
+template <int KIND, bool FAST, int ADAPT = 0>
 __device__ __forceinline__ void escape_angle_lane(const cvk::MetricParams &M, double alpha, double l_cam, unsigned max_iter, double max_radius,
-                                                  double delta, int fast_ok, double &angle, double &space, unsigned &steps_out, int &status) {
+                                                  double delta, int fast_ok, double &angle, double &space, unsigned &steps_out, int &status,
+                                                  [[maybe_unused]] double kappa = 0.0) {
   double sa, ca;
   cv_sincos(alpha, &sa, &ca);
   const double pos[4] = {0.0, l_cam, CV_PI / 2.0, 0.0};
@@ -42,7 +48,8 @@ __device__ __forceinline__ void escape_angle_lane(const cvk::MetricParams &M, do
     unsigned k = 0;
     for (;;) {
       ++k;
-      one_step<KIND, true, FAST, true>(M, delta, q, lane_ok); /* equatorial photons: see ray_step_fast */
+      if constexpr (ADAPT != 0) one_step<KIND, true, FAST, true>(M, cvk::step_delta(delta, kappa, q.l), q, lane_ok);
+      else one_step<KIND, true, FAST, true>(M, delta, q, lane_ok); /* equatorial photons: see ray_step_fast */
       const bool esc = ray_escaped(q.l, max_radius);
       const unsigned long long em = __builtin_amdgcn_ballot_w64(esc);
       if (em) {
@@ -73,8 +80,8 @@ __device__ __forceinline__ void escape_angle_lane(const cvk::MetricParams &M, do
 }
 
 /* K2: compute_escape_angle for a batch of alphas (the host-paced sampler's launches: efficient_host.h eval_escape_batch) */
-template <int KIND, bool FAST>
-__global__ __launch_bounds__(64) void escape_angle_kernel(const EscapeAngleParams P) {
+template <int KIND, bool FAST, int ADAPT = 0>
+__global__ __launch_bounds__(64) void escape_angle_kernel(const std::conditional_t<ADAPT != 0, EscapeAngleParamsAdapt, EscapeAngleParams> P) {
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -83,7 +90,10 @@ __global__ __launch_bounds__(64) void escape_angle_kernel(const EscapeAngleParam
   double angle, space;
   unsigned steps;
   int status;
-  escape_angle_lane<KIND, FAST>(M, P.alpha[i], P.l_cam[i], P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status);
+  if constexpr (ADAPT != 0)
+    escape_angle_lane<KIND, FAST, 1>(M, P.alpha[i], P.l_cam[i], P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status, P.kappa);
+  else
+    escape_angle_lane<KIND, FAST>(M, P.alpha[i], P.l_cam[i], P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status);
   P.angle[i] = angle;
   P.space[i] = space;
   P.steps[i] = steps;
@@ -120,11 +130,14 @@ struct SamplerParams {
   int *spec_status;
   int speculate;                  /* 0: every round integrates exactly its pending points (no subtree, table still used) */
 };
+struct SamplerParamsAdapt : SamplerParams { /* the ADAPT instantiation's argument: as EscapeAngleParamsAdapt */
+  double kappa;
+};
 constexpr unsigned kSamplerThreads = 512; /* two waves per SIMD: what a lone chain leaves idle anyway (a step is ~85 dependent FP64
                                              instructions of ~8 cycles latency, issued in 4) */
 
-template <int KIND, bool FAST>
-__global__ __launch_bounds__(kSamplerThreads) void sampler_kernel(const SamplerParams P) {
+template <int KIND, bool FAST, int ADAPT = 0>
+__global__ __launch_bounds__(kSamplerThreads) void sampler_kernel(const std::conditional_t<ADAPT != 0, SamplerParamsAdapt, SamplerParams> P) {
   __shared__ MathTablesLds<KIND> s_tab;
   __shared__ cvk::SamplerState S;
   __shared__ int s_panic;
@@ -193,7 +206,10 @@ __global__ __launch_bounds__(kSamplerThreads) void sampler_kernel(const SamplerP
           double angle, space;
           unsigned steps;
           int status;
-          escape_angle_lane<KIND, FAST>(M, S.eval_a[k], l_cam, P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status);
+          if constexpr (ADAPT != 0)
+            escape_angle_lane<KIND, FAST, 1>(M, S.eval_a[k], l_cam, P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status, P.kappa);
+          else
+            escape_angle_lane<KIND, FAST>(M, S.eval_a[k], l_cam, P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status);
           const unsigned slot = S.eval_slot[k];
           CV_SPEC_ST(&T.e[slot], angle);
           CV_SPEC_ST(&T.s[slot], space);
@@ -463,11 +479,14 @@ struct DirectParams {
   unsigned char *fb;
   FrameCounters counters;
 };
+struct DirectParamsAdapt : DirectParams { /* the ADAPT instantiations' argument: as EscapeAngleParamsAdapt */
+  double kappa;
+};
 
 /* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
-template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0> /* FILTER: option "sky_filter", PROJ: option "projection" */
+template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter", PROJ: option "projection", ADAPT: option "step_scale" */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 4 : 6)))
-void direct_kernel(const DirectParams P) {
+void direct_kernel(const std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams> P) {
   [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */
   if constexpr (SS > 1) texel_ss = 0xFF000000u;
   __shared__ MathTablesLds<KIND> s_tab;
@@ -491,7 +510,8 @@ void direct_kernel(const DirectParams P) {
     int code = cvk::CODE_NONE;
     /* a per-lane loop (lanes outside the frame are idle from the start, so the counter is not wave-uniform) */
     for (unsigned k = 0; k < P.max_iter; ++k) {
-      one_step<KIND, true, FAST, true>(M, P.delta, q, lane_ok);
+      if constexpr (ADAPT != 0) one_step<KIND, true, FAST, true>(M, cvk::step_delta(P.delta, P.kappa, q.l), q, lane_ok);
+      else one_step<KIND, true, FAST, true>(M, P.delta, q, lane_ok);
       ++steps;
       if (ray_escaped(q.l, P.max_radius)) {
         code = escape_code(q.l);

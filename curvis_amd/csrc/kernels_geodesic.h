@@ -36,6 +36,16 @@ struct IntegrateParams {
    * XCC_ID}; null in normal operation */
   unsigned long long *trace;
 };
+/* The argument of the ADAPT instantiations (option "step_scale", cv_device.h step_delta): IntegrateParams with two members appended.
+ * The other kernels keep IntegrateParams itself, so not one of their argument loads moves -- the hidden arguments behind the struct
+ * (workgroup size) included.  kappa = RN(delta / L0); t_out: the debug dump's x[0] per pixel, integrated on the device (the host's
+ * replay_debug_time assumes one delta). */
+struct IntegrateParamsAdapt : IntegrateParams {
+  double kappa;
+  double *t_out;
+};
+template <int ADAPT>
+using IntegrateArgs = std::conditional_t<ADAPT != 0, IntegrateParamsAdapt, IntegrateParams>;
 
 struct ShadeParams {
   cvk::MetricParams metric;
@@ -231,13 +241,16 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
  * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame.
  * SS: supersampling factor (1: one ray per output pixel; 2, 4, 8: P is in units of the fine grid and the epilogue averages,
  * kernels_epilogue.h resolve_store; FUSED only). */
-template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0> /* FILTER: option "sky_filter" (FUSED only);
-  PROJ: 0 the reference's perspective mapping, 1 option "projection" != 0 (P.projection says which; FUSED only) */
+template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter" (FUSED only);
+  PROJ: 0 the reference's perspective mapping, 1 option "projection" != 0 (P.projection says which; FUSED only);
+  ADAPT: 1 option "step_scale" != 0: every step takes cv_device.h step_delta(P.delta, P.kappa, l) instead of P.delta (the fused kernels and
+  the debug dump's staged PHI kernel, fast step only) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
-void geodesic_static(const IntegrateParams P) {
+void geodesic_static(const IntegrateArgs<ADAPT> P) {
   static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");
   static_assert(FILTER == 0 || (FUSED && !PHI), "the filtered lookup exists in the fused epilogues only");
   static_assert(PROJ == 0 || (FUSED && !PHI), "the projections exist in the fused kernels only");
+  static_assert(ADAPT == 0 || (FAST && (FUSED != PHI)), "scaled steps exist for the fast step, in the fused kernels and the debug dump's");
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -249,8 +262,10 @@ void geodesic_static(const IntegrateParams P) {
   bool valid = false, active = false, lane_ok_w = false;
   unsigned steps = 0;
   int code = cvk::CODE_NONE;
+  [[maybe_unused]] double t = 0.0; /* ADAPT debug dump: x[0], the reference's t + (p_t g^tt) delta_k with p_t = 1, g^tt = -1 */
   if (id < P.total_rays && decode_ray(P, id, frame, px, py)) {
     cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
+    if constexpr (ADAPT != 0 && PHI) t = P.cams[frame].pos[0];
     lane_ok_w = FAST && P.fast_ok && cvk::ray_fast_ok(q);
     valid = true;
     active = P.max_iter != 0;
@@ -268,7 +283,13 @@ void geodesic_static(const IntegrateParams P) {
     steps = P.max_iter;
     for (;;) {
       ++k;
-      one_step<KIND, PHI, FAST>(M, P.delta, q, lane_ok_w);
+      if constexpr (ADAPT != 0) {
+        const double dk = cvk::step_delta(P.delta, P.kappa, q.l);
+        one_step<KIND, PHI, FAST>(M, dk, q, lane_ok_w);
+        if constexpr (PHI) t = t + (1.0 * -1.0) * dk;
+      } else {
+        one_step<KIND, PHI, FAST>(M, P.delta, q, lane_ok_w);
+      }
       const bool esc = ray_escaped(q.l, P.max_radius);
       const unsigned long long em = __builtin_amdgcn_ballot_w64(esc);
       if (em) { /* rare: at most 64 times per wave.  The volatile asm keeps this a real (scalar) branch. */
@@ -302,6 +323,7 @@ void geodesic_static(const IntegrateParams P) {
       none = (code == cvk::CODE_NONE);
     } else {
       store_ray<PHI>(P.store, slot, q, steps, code);
+      if constexpr (ADAPT != 0) P.t_out[slot] = t;
     }
   }
   if constexpr (SS > 1) resolve_store<SS>(P.fb, P.W, P.H, frame, px, py, valid, seen); /* the whole wave: lanes outside the frame add nothing */

@@ -41,6 +41,7 @@ struct curvis_ctx {
   bool streams_pending = false;
   Event ev_streams;
   DeviceBuffer<curvis_ray_debug> d_dbg;
+  DeviceBuffer<double> d_dbg_t;         /* option "step_scale": x[0] of every ray of a debug dump, integrated on the device */
   DeviceBuffer<unsigned char> d_store;  /* RayStore arrays, carved from one allocation */
   DeviceBuffer<unsigned char> d_rq;     /* RelayQueue + ticket ring of the relay kernel */
   DeviceBuffer<unsigned char> d_verify; /* copy of the relay kernel's frame while the static kernel re-renders it (seat belt) */
@@ -105,6 +106,9 @@ struct curvis_ctx {
                                direction, defined in include/curvis_hip.h (cv_device.h sky_bilinear_taps / sky_bilinear_blend) */
   int projection = 0;       /* 0: the reference's perspective camera; 1: equirectangular; 2: equidistant fisheye -- pixel -> camera-space
                                vector, defined in include/curvis_hip.h (cv_device.h camera_pixel_vector) */
+  int64_t step_scale = 0;   /* S in [0, 2^20]; 0: every Euler step takes the call's delta (the reference).  S != 0: L0 = S / 256, and a step
+                               from radial coordinate l takes max(delta, |l| delta / L0) -- defined in include/curvis_hip.h (cv_device.h
+                               step_delta) */
   int sampling_speculation = -1; /* efficient renderer: depth of the speculative subtree evaluated below every
                                     refined interval (0 = one launch per refinement round, no speculation;
                                     -1 = automatic: 10 for one or two frames, 6 for three to five, 4 for larger batches;
@@ -122,6 +126,7 @@ struct curvis_ctx {
     uint32_t n_frames = 0, max_iter = 0, alpha_nums = 0, max_iterations_sampling = 0;
     double max_radius = 0, delta = 0, thr1 = 0, thr2 = 0;
     int fast = 0, speculate = 0;
+    int64_t step_scale = 0; /* option "step_scale": other steps, other tables */
     std::vector<double> l_frame; /* radial coordinate of every frame's camera */
   };
   struct SamplerSlot {
@@ -188,18 +193,24 @@ auto with_flag(bool flag, F &&f) {
  * with_launch_shape(kind, fast, ss, filter, projection, [&](auto S) { using T = decltype(S); ... T::KIND, T::FAST, T::SS, T::FILTER,
  * T::PROJ ... }) calls the lambda once.  ss is 1, 2, 4 or 8 and filter 0 or 1: the writers of the options "supersample" and
  * "sky_filter" admit nothing else.  PROJ is 1 for every projection but the perspective one: which of them is a kernel argument. */
-template <int KIND_, bool FAST_, int SS_, int FILTER_, int PROJ_>
+template <int KIND_, bool FAST_, int SS_, int FILTER_, int PROJ_, int ADAPT_ = 0>
 struct LaunchShape {
-  static constexpr int KIND = KIND_, SS = SS_, FILTER = FILTER_, PROJ = PROJ_;
+  static constexpr int KIND = KIND_, SS = SS_, FILTER = FILTER_, PROJ = PROJ_, ADAPT = ADAPT_;
   static constexpr bool FAST = FAST_;
 };
+/* adapt: option "step_scale" != 0 (ADAPT = 1 exists for the fast step only: prepare_call_shape refuses the option with fast_math = 0) */
 template <typename F>
-auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, uint32_t projection, F &&f) {
+auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, uint32_t projection, bool adapt, F &&f) {
   return with_kind(kind, [&](auto K) {
     return with_flag(fast, [&](auto A) {
       auto with_ss = [&](auto N) {
         constexpr int KIND = decltype(K)::value, SS = decltype(N)::value;
         constexpr bool FAST = decltype(A)::value;
+        if constexpr (FAST)
+          if (adapt) {
+            if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1, 1>{});
+            return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0, 1>{});
+          }
         if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1>{});
         return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0>{});
       };
@@ -222,11 +233,26 @@ constexpr uint32_t kSkyFilterMaxSide = 1u << 23;
  * of it is pixel (x, y) of the original, cv_device.h ray_init). */
 struct CallShape {
   uint32_t ss = 1, filter = 0, projection = 0;
+  double kappa = 0.0; /* option "step_scale" != 0: RN(delta / L0), else 0 (never read) */
+  bool adapt = false; /* option "step_scale" != 0 */
   std::vector<curvis_camera> fine;
 };
+/* Option "step_scale" for a call with step delta: off (adapt = false), or kappa = RN(delta / L0) with L0 = S / 256 (exact), one IEEE
+ * division, here and nowhere else.  The option needs a positive delta and the fast step (the strict step exists for the theorem about
+ * the reference's own frames, and has no ADAPT kernels). */
+int step_scale_kappa(curvis_ctx *ctx, double delta, double &kappa, bool &adapt) {
+  kappa = 0.0;
+  adapt = ctx->step_scale != 0;
+  if (!adapt) return CURVIS_OK;
+  if (!(delta > 0.0)) return fail(ctx, CURVIS_E_INVALID, "step_scale != 0: the step delta must be greater than 0");
+  if (ctx->fast_math == 0) return fail(ctx, CURVIS_E_INVALID, "step_scale != 0: fast_math = 0 (the strict step) takes the reference's fixed step only (set step_scale = 0)");
+  kappa = cvk::step_kappa(delta, ctx->step_scale);
+  return CURVIS_OK;
+}
 /* cams: the caller's n_frames cameras on entry, those the kernels run over on return (s.fine with ss > 1).  With the filter on, both
  * skies must be small enough for it; a fisheye whose image corner lies beyond the angle pi from the axis is refused; too_large is the renderer's message for a fine resolution that no longer fits 32 bits. */
-int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_frames, const char *too_large, CallShape &s) {
+int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_frames, double delta, const char *too_large, CallShape &s) {
+  if (int rc = step_scale_kappa(ctx, delta, s.kappa, s.adapt)) return rc;
   s.ss = (uint32_t)ctx->supersample;
   s.filter = (uint32_t)ctx->sky_filter;
   if (s.filter)
@@ -461,13 +487,20 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
 /* One launch of the integrator.  relay: 0 no, 1 the relay kernel, 2 its relay-only re-launch.  The unfused static kernel and the
  * persistent one exist for SS = 1, FILTER = 0, PROJ = 0 only (their static_asserts): render_impl refuses the call shapes that would need
  * more. */
-template <int KIND, bool PHI, bool FAST, int SS, int FILTER, int PROJ>
-int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int relay) {
-  if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, P, relay == 2);
+template <int KIND, bool PHI, bool FAST, int SS, int FILTER, int PROJ, int ADAPT = 0>
+int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused, int relay) {
+  const IntegrateParams &P = PA; /* what every kernel but the ADAPT ones takes */
+  if constexpr (ADAPT == 0) /* scaled steps never take the relay kernel (choose_render_path) */
+    if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, P, relay == 2);
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const dim3 grid((unsigned)((P.total_rays + bt - 1ull) / bt));
   bool staged = false; /* launched a kernel that leaves the shading to shade_kernel */
-  if constexpr (SS == 1 && FILTER == 0 && PROJ == 0) {
+  if constexpr (ADAPT != 0) { /* the fused kernel, or the debug dump's staged one; render_impl refuses every other shape */
+    if constexpr (PHI) {
+      hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, false, 1, 0, 0, 1>), grid, dim3(bt), 0, ctx->stream, PA);
+      staged = true;
+    }
+  } else if constexpr (SS == 1 && FILTER == 0 && PROJ == 0) {
     if (ctx->variant == 0) {
       int per_cu = ctx->blocks_per_cu;
       if (per_cu <= 0) {
@@ -485,19 +518,21 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParams &P, bool fused, int 
       staged = true;
     }
   }
-  if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ>), grid, dim3(bt), 0, ctx->stream, P);
+  if constexpr (ADAPT != 0 && !PHI) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ, 1>), grid, dim3(bt), 0, ctx->stream, PA);
+  if constexpr (ADAPT == 0)
+    if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ>), grid, dim3(bt), 0, ctx->stream, P);
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
 
 /* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled, never filtered and always in perspective */
-int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParams &P, uint32_t ss,
-                         uint32_t filter) {
-  return with_launch_shape(kind, fast, ss, filter, (uint32_t)P.projection, [&](auto S) {
+int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParamsAdapt &P, uint32_t ss,
+                         uint32_t filter, bool adapt) {
+  return with_launch_shape(kind, fast, ss, filter, (uint32_t)P.projection, adapt, [&](auto S) {
     using T = decltype(S);
     if constexpr (T::SS == 1 && T::FILTER == 0 && T::PROJ == 0)
-      if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0, 0>(ctx, P, false, 0);
-    return launch_integrate<T::KIND, false, T::FAST, T::SS, T::FILTER, T::PROJ>(ctx, P, fused, relay);
+      if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0, 0, T::ADAPT>(ctx, P, false, 0);
+    return launch_integrate<T::KIND, false, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>(ctx, P, fused, relay);
   });
 }
 
@@ -543,6 +578,8 @@ struct BruteCall {
                                     RAY grid (what the kernels run over); npix and fb_bytes are always those of the frames written */
   uint32_t filter;               /* option "sky_filter" for this call */
   uint32_t projection;           /* option "projection" for this call */
+  double kappa = 0.0;            /* option "step_scale" for this call: RN(delta / L0) ... */
+  bool adapt = false;            /* ... and whether it is on */
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
   size_t npix = 0, fb_bytes = 0;
 };
@@ -577,7 +614,9 @@ RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
   const unsigned long long relay_min = ctx->relay_min_blocks >= 0 ? (unsigned long long)ctx->relay_min_blocks
                                                                    : 4ull * (unsigned long long)ctx->prop.multiProcessorCount;
   const size_t relay_staging = (size_t)tiles * 64u * kStoreBytesPerPixel;
-  p.relay = (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
+  /* option "step_scale": the static kernel -- the relay segments are sized in fixed-delta steps and its hand-over pattern was tuned on
+   * fixed-delta step counts */
+  p.relay = !c.adapt && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
             relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
   p.chunk = c.n_frames;
   p.store_bytes = p.relay ? relay_staging : 0;
@@ -604,7 +643,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   int rc = prepare_counters(ctx, nf, FC);
   if (rc) return rc;
   const size_t cnt_words = counter_words(nf, FC.slots);
-  IntegrateParams P;
+  IntegrateParamsAdapt P;
   P.metric = MP;
   P.cams = ctx->d_cams + f0;
   P.n_frames = nf;
@@ -627,6 +666,8 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   P.refill_threshold = ctx->refill_threshold < 1 ? 1 : (ctx->refill_threshold > 64 ? 64 : ctx->refill_threshold);
   P.fast_ok = cvk::metric_fast_ok(c.metric->kind, MP, c.max_radius) ? 1 : 0;
   P.projection = (int)c.projection;
+  P.kappa = c.kappa;
+  P.t_out = (c.adapt && c.dbg_out) ? ctx->d_dbg_t + (size_t)f0 * c.npix : nullptr;
   /* diagnostics only (CURVIS_TRACE_FILE): per-wave records of this launch, binary u64 x 4 per wave */
   DeviceBuffer<unsigned long long> trace;
   const char *trace_file = getenv("CURVIS_TRACE_FILE");
@@ -649,7 +690,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   Q.counters = FC;
 
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P, c.ss, c.filter);
+  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P, c.ss, c.filter, c.adapt);
   if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   if (trace) {
@@ -695,7 +736,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
     if (hq->finished >= n_tiles) break;
     if (ctx->last_relay_launches++ > 64)
       return fail(ctx, CURVIS_E_HIP, "relay kernel: tiles still unfinished after 64 relay launches");
-    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P, c.ss, c.filter);
+    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P, c.ss, c.filter, c.adapt);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
@@ -864,6 +905,7 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
   if ((rc = fb_begin_write(ctx, c.fb_bytes))) return rc;
   ctx->fb_bytes = c.fb_bytes;
   if (c.dbg_out && (rc = ctx->d_dbg.reserve(ctx, c.npix * c.n_frames))) return rc;
+  if (c.dbg_out && c.adapt && (rc = ctx->d_dbg_t.reserve(ctx, c.npix * c.n_frames))) return rc;
   const RenderPath path = choose_render_path(ctx, c);
   if (path.store_bytes && (rc = ctx->d_store.reserve(ctx, path.store_bytes))) return rc;
   if ((rc = ctx->d_cams.reserve(ctx, c.n_frames))) return rc;
@@ -893,7 +935,13 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
   } else {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
-  if (c.dbg_out) replay_debug_time(c);
+  if (c.dbg_out && c.adapt) { /* x[0] was integrated on the device, step by step with the ray's own delta_k */
+    std::vector<double> t(c.npix * c.n_frames);
+    HIP_TRY(ctx, hipMemcpy(t.data(), ctx->d_dbg_t, sizeof(double) * t.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < t.size(); ++i) c.dbg_out[i].x[0] = t[i];
+  } else if (c.dbg_out) {
+    replay_debug_time(c);
+  }
   if (c.stats) {
     counts_to_stats(tot.counts, *c.stats);
     c.stats->kernel_ms = tot.integrate_ms + tot.shade_ms;
@@ -911,27 +959,38 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
   BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u, 0u};
-  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->projection)) return render_rays(ctx, c);
+  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->projection && !ctx->step_scale)) return render_rays(ctx, c);
   /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under
-   * the name of the projection when it is on, else of the filter when that is on, of the supersampling otherwise */
-  const bool f = ctx->sky_filter != 0, p = ctx->projection != 0;
+   * the name of the projection when it is on, else of the filter when that is on, else of the supersampling when that is on.  The scaled
+   * steps (option "step_scale") exist in the fused kernels and in the debug dump's: a shape with a message of its own in the last
+   * column is refused under the option's name when none of the other three refuses it.  The option's fourth refusal, fast_math = 0,
+   * holds for all three renderers and is therefore made where they all pass, in step_scale_kappa (prepare_call_shape). */
+  const bool f = ctx->sky_filter != 0, p = ctx->projection != 0, n = ctx->supersample > 1, a = ctx->step_scale != 0;
   const struct {
     bool refused;
-    const char *projection, *filter, *supersample;
+    const char *projection, *filter, *supersample, *step_scale;
   } shapes[3] = {
       {dbg_out != nullptr, "projection != 0: the debug dump replays the perspective camera (set projection = 0)",
        "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)",
-       "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)"},
+       "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)", nullptr},
       {ctx->variant == 0, "projection != 0: variant = 0 (the persistent kernel) has the perspective camera only",
        "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
-       "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve"},
+       "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve",
+       "step_scale != 0: variant = 0 (the persistent kernel) takes the reference's fixed step only"},
       {ctx->fuse_shade == 0, "projection != 0: fuse_shade = 0 (the unfused static kernel) has the perspective camera only",
        "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
-       "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve"}};
+       "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve",
+       dbg_out ? nullptr : "step_scale != 0: fuse_shade = 0 (the unfused static kernel) takes the reference's fixed step only outside the debug dump"}};
   for (const auto &s : shapes)
-    if (s.refused) return fail(ctx, CURVIS_E_INVALID, p ? s.projection : f ? s.filter : s.supersample);
+    if (s.refused) {
+      const char *why = p ? s.projection : f ? s.filter : n ? s.supersample : nullptr;
+      if (!why && a) why = s.step_scale;
+      if (why) return fail(ctx, CURVIS_E_INVALID, why);
+    }
   CallShape shape;
-  if (int rc = prepare_call_shape(ctx, c.cams, n_frames, "frame or batch too large", shape)) return rc;
+  if (int rc = prepare_call_shape(ctx, c.cams, n_frames, delta, "frame or batch too large", shape)) return rc;
+  c.kappa = shape.kappa;
+  c.adapt = shape.adapt;
   c.ss = shape.ss;
   c.filter = shape.filter;
   c.projection = shape.projection;

@@ -777,12 +777,28 @@ def check_projection(projection):
     return PROJECTIONS.index(projection)
 
 
+STEP_SCALE_MAX = 1 << 20  # library option "step_scale": S = L0 x 256, an integer in [0, 2^20]
+
+
+def check_step_scale(step_scale):
+    """the coordinate distance L0 inside which the Euler step is the reference's (outside it the step grows as |l| / L0) as the library
+    option's integer S = 256 L0, or ValueError: a number that is a multiple of 1/256 in [0, 4096]; 0 (the default) switches it off"""
+    ok = not isinstance(step_scale, bool) and isinstance(step_scale, (int, float, np.integer, np.floating))
+    if ok:
+        scaled = float(step_scale) * 256.0  # exact, or inf / nan
+        ok = scaled == scaled and 0.0 <= scaled <= STEP_SCALE_MAX and scaled == int(scaled)
+    if not ok:
+        raise ValueError("step_scale must be 0 (off) or a multiple of 1/256 up to 4096")
+    return int(scaled)
+
+
 class _Supersampled:
     """the context's "supersample" option set to `factor` -- and "sky_filter" to `sky_filter` (0 or 1), "projection" to `projection`
-    (0, 1 or 2) -- for the duration of a render call, then put back"""
+    (0, 1 or 2), "step_scale" to `step_scale` (the integer S) -- for the duration of a render call, then put back"""
 
-    def __init__(self, context, factor, sky_filter=0, projection=0):
-        self.context, self.want = context, (("supersample", factor), ("sky_filter", sky_filter), ("projection", projection))
+    def __init__(self, context, factor, sky_filter=0, projection=0, step_scale=0):
+        self.context, self.want = context, (("supersample", factor), ("sky_filter", sky_filter), ("projection", projection),
+                                            ("step_scale", step_scale))
 
     def __enter__(self):
         self.before = [self.context.get_option(key) for key, _ in self.want]
@@ -802,7 +818,8 @@ class RelativisticSystem:
     reference): N x N rays per pixel, averaged on the device into the camera's resolution; and sky_filter="nearest" (the
     reference's lookup) or "bilinear" (not in the reference: the four texels around a ray's direction, blended on the device); and
     projection="perspective" (the reference's camera), "equirectangular" or "fisheye" (not in the reference: library option
-    "projection")."""
+    "projection"); and step_scale=L0 (not in the reference; 0, the default, is its fixed step): outside the coordinate distance L0, a
+    multiple of 1/256, a ray's Euler step grows as |l| / L0 (library option "step_scale")."""
 
     def __init__(self, metric, background_positive, background_negative, camera, context=None):
         self.metric = metric
@@ -819,34 +836,40 @@ class RelativisticSystem:
         if ctx._sky_objs[1] is not self.background_negative:
             ctx.set_sky(1, self.background_negative)
 
-    def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective"):
+    def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
+                     step_scale=0.0):
         """The per-pixel renderer; returns an HxWx3 uint8 array (DynamicImage::ImageRgb8)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
+        scale = check_step_scale(step_scale)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj):
+        with _Supersampled(self.context, factor, filt, proj, scale):
             rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
         self.last_stats = st
         return rgb
 
     def render_image_efficient(self, max_iterations_propagation, max_radius, delta, alpha_nums,
                                max_iterations_sampling, sampling_convergence_threshold_1,
-                               sampling_convergence_threshold_2, supersample=1, sky_filter="nearest", projection="perspective"):
+                               sampling_convergence_threshold_2, supersample=1, sky_filter="nearest", projection="perspective",
+                               step_scale=0.0):
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
+        scale = check_step_scale(step_scale)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj):
+        with _Supersampled(self.context, factor, filt, proj, scale):
             rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
                                                     alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
                                                     sampling_convergence_threshold_2)
         self.last_stats = st
         return rgb
 
-    def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective"):
+    def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
+                            step_scale=0.0):
         """NOT in the reference: the image render_image_efficient approximates, with compute_escape_angle evaluated
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
+        scale = check_step_scale(step_scale)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj):
+        with _Supersampled(self.context, factor, filt, proj, scale):
             rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
         self.last_stats = st
         return rgb

@@ -195,6 +195,12 @@ int curvis_vector_to_direction(const curvis_metric *metric, const double positio
  * step of (x, p_cov) in place, on the host, with the IEEE form of the step the kernels fall back to (the fast step
  * returns the same bits) -- the body of curvis_photon_trajectories' loop, all eight components. */
 int curvis_update_relativistic_object(const curvis_metric *metric, double x[4], double p_cov[4], double delta);
+/* Option "step_scale" (defined with the options below) for ONE step: *out = delta_k, the step a render call with step `delta` under
+ * step_scale = S takes from a ray whose radial coordinate before the step is l -- kappa formed as the render calls form it, then
+ * cv_device.h step_delta, the text the kernels' loops call.  S = 0 gives delta.  CURVIS_E_INVALID for S outside [0, 2^20], a null
+ * `out`, and S != 0 with !(delta > 0).  Fed into curvis_update_relativistic_object it walks a ray the way the kernels do. */
+#define CURVIS_STEP_SCALE_MAX (1u << 20)
+int curvis_step_delta(double delta, int64_t step_scale, double l, double *out);
 /* SphericalImage::get_pixel_from_vector3's texel (src/images.rs:115-142, 171-174; src/algebra.rs:106-134) for an image of
  * w x h texels whose inverse orientation is inv_rot (NULL = the default forward x / up z): raw `as u32` indices.
  * Returns CURVIS_OK, or CURVIS_E_INVALID with the indices still set when x == w or y == h (the reference's
@@ -437,6 +443,27 @@ int curvis_ctx_download_wait(curvis_ctx *ctx);
  * traced.  Refused with CURVIS_E_INVALID while projection != 0, as under the two options above: curvis_render_brute_debug,
  * "variant" = 0 and "fuse_shade" = 0 (only the fused kernels have the projections).  The relay seat belt checks a projected launch
  * shape on its own),
+ * "step_scale" (an integer S, 0 <= S <= 2^20, default 0 = off: every Euler step takes the call's delta, the reference's loop bit for
+ * bit and the kernels that exist without the option; anything else is refused with CURVIS_E_INVALID and the old value stays.  For
+ * S != 0 and a render call with step delta:
+ *   1. L0 = (double)S / 256.0 (exact): the coordinate distance inside which the step is the reference's.
+ *   2. kappa = RN(delta / L0), formed once per call on the host with one IEEE double division.
+ *   3. Step k of a ray whose radial coordinate BEFORE the step is l_k uses a = RN(|l_k| kappa) and delta_k = (a > delta) ? a : delta;
+ *      a NaN l_k therefore gives delta.  (The code, cv_device.h step_delta, forms it as the IEEE maximum fmax(a, delta): the same value for
+ *      every input a render call admits -- a > delta gives a, a <= delta gives delta, and for a NaN a the maximum returns its other
+ *      operand, delta, which is a number because delta > 0 is checked on the host -- and one instruction on the device.)
+ *   4. The step itself is the reference's update_relativistic_object with delta_k in place of delta: operations, order and roundings
+ *      are otherwise unchanged, and the fast step keeps its contract (correctly rounded quotients).
+ *   5. The escape test after each step, the max_iterations cap counted in steps, new_photon, direction, lookup and every counter
+ *      are unchanged; `steps` counts executed steps, so it becomes smaller.
+ *   6. In the debug dump x[0] follows the reference's line with the same delta_k: t_{k+1} = t_k + (1.0 * -1.0) * delta_k.
+ * All three renderers honour it (the efficient renderer in both samplers; its per-pixel kernel never integrates); it combines with
+ * "supersample", "sky_filter" and "projection", row bands, batches and the prefetch, whose jobs it is part of.  With S != 0 the brute
+ * renderer launches the static kernel, never the relay kernel.  A render call with S != 0 and !(delta > 0) fails with
+ * CURVIS_E_INVALID; so do, while S != 0, "fast_math" = 0 (every renderer), "variant" = 0 and, outside the debug dump,
+ * "fuse_shade" = 0.  curvis_render_brute_debug is served (when none of the three options above is on).
+ * curvis_photon_trajectories, curvis_compute_escape_angles and curvis_update_relativistic_object take their delta explicitly and
+ * do not look at the option; curvis_step_delta evaluates step 3 on the host),
  * "max_store_bytes" (ray-store budget that bounds the frames per launch of a batch),
  * "sampling_speculation" (efficient renderer: depth of the speculative dyadic subtree evaluated below every
  * refined interval; 0 = one launch per refinement round; default -1 = automatic, 10 for one or two frames, 6 for three to five and 4

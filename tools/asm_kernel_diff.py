@@ -69,10 +69,12 @@ def main():
     names = demangle(sorted(set(b0) | set(b1)))
     # a kernel template that gained a trailing template parameter whose default (1: a factor, 0: a switch) is what it was before, or
     # a kernel that became a template with such a parameter (then "void name<0>(...)"): paired with its old name
-    old_of = {names[n]: n for n in b0}
+    # (names are paired without their parameter lists: the type of a kernel's argument may be spelled through the new parameter)
+    head = lambda d: d.replace("(anonymous namespace)::", "").split("(")[0] + "("  # noqa: E731
+    old_of = {head(names[n]): n for n in b0}
     for pattern, to in ((r", 0>\(", ">("), (r"^void (.*)<0>\(", r"\1("), (r", 1>\(", ">(")):
-        for n in [n for n in b1 if n not in b0 and re.search(pattern, names[n])]:
-            was = old_of.get(re.sub(pattern, to, names[n], count=1))
+        for n in [n for n in b1 if n not in b0 and re.search(pattern, head(names[n]))]:
+            was = old_of.get(re.sub(pattern, to, head(names[n]), count=1))
             if was is not None and was not in b1:
                 b1[was], u1[was] = b1.pop(n), u1.pop(n, {})
                 names[was] = names.pop(n)
