@@ -565,6 +565,14 @@ int curvis_step_delta(double delta, int64_t step_scale, double l, double *out) {
   return cvk::step_delta_of_scale(delta, (long long)step_scale, l, out) ? CURVIS_OK : CURVIS_E_INVALID;
 }
 
+int curvis_heun_step(const curvis_metric *metric, double x[4], double p_cov[4], double delta) {
+  if (!metric || !x || !p_cov) return CURVIS_E_INVALID;
+  if (curvis_metric_validate(metric) != CURVIS_OK) return CURVIS_E_METRIC;
+  const cvk::MetricParams MP = make_metric(*metric);
+  with_kind(metric->kind, [&](auto K) { cvk::heun_step_all<decltype(K)::value>(MP, x, p_cov, delta); });
+  return CURVIS_OK;
+}
+
 int curvis_sky_texel_index(uint32_t w, uint32_t h, const double inv_rot[9], const double v[3], uint32_t *x, uint32_t *y) {
   if (!v || !x || !y || w == 0 || h == 0) return CURVIS_E_INVALID;
   cvk::SkyParams S;
@@ -959,6 +967,12 @@ const OptionEntry kOptions[] = {
      [](curvis_ctx *c, int64_t v) -> int {
        if (v < 0 || v > (int64_t)CURVIS_STEP_SCALE_MAX) return fail(c, CURVIS_E_INVALID, "step_scale must be 0 (off) or L0 x 256 in 1 .. 2^20");
        c->step_scale = v;
+       return CURVIS_OK;
+     }},
+    {"integrator", OPT_READ(c->integrator),
+     [](curvis_ctx *c, int64_t v) -> int {
+       if (v != 0 && v != 1) return fail(c, CURVIS_E_INVALID, "integrator must be 0 (Euler) or 1 (Heun)");
+       c->integrator = (int)v;
        return CURVIS_OK;
      }},
     OPT_RW(device_sampler, int),

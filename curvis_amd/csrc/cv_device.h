@@ -413,6 +413,8 @@ CV_HD void ray_step_fast(const MetricParams &M, Ray &q, double delta, bool lane_
   /* guard (branch-free, one compare each): sin(theta) and l non-zero, not NaN and far from the underflow
    * limit.  Upper bounds are implied: |sin| <= 1, and a step is only executed for a ray that has not
    * escaped, |l| <= max_radius < 2^90 (metric_fast_ok; an infinite l has escaped, a NaN fails the compare).
+   * (The second stage of a Heun step starts from a state nobody tested: ray_step_heun clears lane_ok for it unless |l| < 2^90,
+   * which is all that the bounds below use.)
    * The Interstellar step tests x = 2(|l| - a)/(pi m) >= 2 instead of l (false for a NaN l): inside |l| < a + pi m
    * -- the throat and the few steps next to it -- a ray takes the strict step; outside, atan x >= atan 2, so r' is
    * far from zero and from the underflow of the quotient's remainder.
@@ -518,6 +520,75 @@ CV_HD void ray_step_fast(const MetricParams &M, Ray &q, double delta, bool lane_
   q.th = q.th + dx2 * delta;
   q.p1 = q.p1 + dp1 * delta;
   q.p2 = q.p2 + dp2 * delta;
+}
+
+/* Option "integrator" = 1 (include/curvis_hip.h): one step of Heun's method, the explicit trapezoid, written as a composition of the
+ * Euler step E this file already has:  y + delta/2 (f(y) + f(y + delta f(y))) = 1/2 (y + E(E(y, delta), delta)).  The state is saved,
+ * the step is taken twice with the SAME delta (under "step_scale" the caller forms it once, from l before the step), and every
+ * integrated component becomes (saved + twice-stepped) * 0.5: one IEEE add, one exact halving.  p_phi is a constant of the step and
+ * is not touched.  One text for host and device: every integrating loop that honours the option calls it, and curvis_heun_step is its
+ * host accessor (FAST = false there).
+ *
+ * The guard of the fast step, re-read for stage states.  ray_step_fast's bounds rest on "a step is only executed FROM a state with
+ * |l| <= max_radius < 2^90" (metric_fast_ok).  The first stage starts from y_k, which has passed the escape test, so nothing changes for
+ * it.  The second stage starts from y' = E(y_k), which is tested by nobody: |l'| = |l + p_l delta_k| lies beyond max_radius on the last
+ * step of almost every escaping ray, and p_l has no bound from the host.  So the second stage carries a per-lane test of its own,
+ * |l'| < 2^90 (false for a NaN and for an infinity), and a lane that fails it takes the strict step, which is always right.  With it
+ * every statement of the guard holds for a stage state by the argument that held for a step state, because each of them used only
+ * |l| < 2^90 and never max_radius itself:
+ *   r^3 < 2^273:  Ellis r^2 = rho^2 + l^2 < 2^181; Interstellar r = rho + m (x atan x - log(1 + x^2)/2) <= rho + m x pi/2 = rho + |l| - a
+ *     < 2^91; flat r = l.
+ *   the dp_l class test:  a non-zero numerator is >= 2^-300 |r'|, with |r'| = |l|/r >= 2^-100 / 2^91 (Ellis; the lower bound on |l| is
+ *     tested inside the step, per stage) or >= (2/pi) atan 2 (Interstellar, x >= 2 tested inside the step, per stage).
+ *   2 max_radius inv_pim < 2^200:  it keeps x = 2(|l| - a)/(pi m) far below overflow; m >= 2^-90 gives inv_pim < 2^90, so
+ *     |l| < 2^90 alone gives x < 2^181.
+ * One v_cmp_lt_f64 with an |l| modifier and one scalar and per Heun step.  Almost every lane passes (2^90 is not a radius any scene
+ * has), so the second stage of a last step is a fast step like the others.
+ *
+ * EQ (the samplers' equatorial shortcut): a ray that keeps theta = fl(pi/2) through both stages keeps it through the average, since
+ * (theta + theta) * 0.5 is exact; a ray whose theta moved in a stage takes the generic step from then on, as under Euler.
+ *
+ * The stages call ray_step_fast under a probe type of their own, HeunStage (as empty as NoProbe): an instantiation apart from the one
+ * the Euler loops call.  With the same instantiation the compiler's inliner, which weighs a function by all of its callers, compiled
+ * the Interstellar direct, escape-angle and sampler kernels of the EULER step with two instructions in another order. */
+struct HeunStage : NoProbe {};
+template <int KIND, bool PHI, bool FAST, bool WIDE_T = false, bool EQ = false>
+CV_HD void ray_step_heun(const MetricParams &M, Ray &q, double delta, bool lane_ok) {
+  const double l0 = q.l, th0 = q.th, p10 = q.p1, p20 = q.p2;
+  [[maybe_unused]] const double ph0 = PHI ? q.ph : 0.0;
+  if (FAST) {
+    ray_step_fast<KIND, PHI, WIDE_T, EQ, HeunStage>(M, q, delta, lane_ok);
+    ray_step_fast<KIND, PHI, WIDE_T, EQ, HeunStage>(M, q, delta, lane_ok && CV_FABS(q.l) < 0x1p90);
+  } else {
+    ray_step<KIND, PHI, WIDE_T>(M, q, delta);
+    ray_step<KIND, PHI, WIDE_T>(M, q, delta);
+  }
+  q.l = (l0 + q.l) * 0.5;
+  q.th = (th0 + q.th) * 0.5;
+  if (PHI) q.ph = (ph0 + q.ph) * 0.5;
+  q.p1 = (p10 + q.p1) * 0.5;
+  q.p2 = (p20 + q.p2) * 0.5;
+}
+/* x[0] of the debug dump over one Heun step: the reference's line t + (p_t g^tt) delta with p_t = 1, g^tt = -1, twice, then averaged */
+CV_HD double heun_time(double t, double delta) {
+  const double t2 = (t + (1.0 * -1.0) * delta) + (1.0 * -1.0) * delta;
+  return (t + t2) * 0.5;
+}
+
+/* the body of the host accessor curvis_heun_step: one Heun step of all eight components of (x, p_cov) in place, with the IEEE form of
+ * the step (ray_step; the fast step returns the same bits).  x[0] takes the reference's line x0 + (p0 g00^-1) delta through both
+ * stages and is averaged like the others; p[0] and p[3] are constants of the step and keep their bits. */
+template <int KIND>
+CV_HD void heun_step_all(const MetricParams &M, double x[4], double p[4], double delta) {
+  Ray q;
+  q.l = x[1], q.th = x[2], q.ph = x[3];
+  q.p1 = p[1], q.p2 = p[2], q.p3 = p[3];
+  q.p3sq = q.p3 * q.p3;
+  ray_step_heun<KIND, true, false>(M, q, delta, false);
+  const double t2 = (x[0] + (p[0] * (1.0 / -1.0)) * delta) + (p[0] * (1.0 / -1.0)) * delta;
+  x[0] = (x[0] + t2) * 0.5;
+  x[1] = q.l, x[2] = q.th, x[3] = q.ph;
+  p[1] = q.p1, p[2] = q.p2;
 }
 
 struct CameraParams {

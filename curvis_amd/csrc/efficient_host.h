@@ -19,14 +19,14 @@ struct EfficientCall {
   uint32_t projection = 0; /* option "projection" for this call */
   uint32_t ss = 1; /* supersampling factor: with ss > 1 `cams` are those of the ss times finer pixel grid (render_efficient_impl) */
   double kappa = 0.0; /* option "step_scale" for this call: RN(delta / L0) ... */
-  bool adapt = false; /* ... and whether it is on: the samplers integrate with step_delta */
+  int adapt = 0; /* ... and the kernels' ADAPT (CallShape): 1 the samplers integrate with step_delta, 2 option "integrator" = 1, with Heun steps */
 };
 
 /* evaluate compute_escape_angle for a batch on the GPU */
 int eval_escape_batch(curvis_ctx *ctx, const curvis_metric *metric, const cvk::MetricParams &MP,
                       const std::vector<double> &alpha, const std::vector<double> &lcam, uint32_t max_iter,
                       double max_radius, double delta, std::vector<double> &angle, std::vector<double> &space,
-                      std::vector<uint32_t> &steps, std::vector<int> &status, double *ms_acc, bool adapt = false, double kappa = 0.0) {
+                      std::vector<uint32_t> &steps, std::vector<int> &status, double *ms_acc, int adapt = 0, double kappa = 0.0) {
   const size_t n = alpha.size();
   angle.resize(n);
   space.resize(n);
@@ -70,7 +70,8 @@ int eval_escape_batch(curvis_ctx *ctx, const curvis_metric *metric, const cvk::M
       const dim3 grid((P.n + 63u) / 64u);
       if constexpr (FAST) /* option "step_scale": the fast step only (step_scale_kappa refuses the other) */
         if (adapt) {
-          hipLaunchKernelGGL((escape_angle_kernel<KIND, true, 1>), grid, dim3(64), 0, ctx->stream, P);
+          if (adapt == 2) hipLaunchKernelGGL((escape_angle_kernel<KIND, true, 2>), grid, dim3(64), 0, ctx->stream, P);
+          else hipLaunchKernelGGL((escape_angle_kernel<KIND, true, 1>), grid, dim3(64), 0, ctx->stream, P);
           return;
         }
       hipLaunchKernelGGL((escape_angle_kernel<KIND, FAST>), grid, dim3(64), 0, ctx->stream, static_cast<const EscapeAngleParams &>(P));
@@ -224,6 +225,7 @@ curvis_ctx::SamplerKey make_sampler_key(const curvis_ctx *ctx, const EfficientCa
   k.fast = ctx->fast_math != 0 ? 1 : 0;
   k.speculate = ctx->sampling_speculation != 0 ? 1 : 0; /* option "sampling_speculation" = 0 switches it off in the kernel too */
   k.step_scale = c.adapt ? ctx->step_scale : 0; /* a prefetch made under another value is another job: it is not consumed */
+  k.integrator = c.adapt == 2 ? 1 : 0;          /* likewise */
   k.l_frame.resize(c.n_frames);
   for (uint32_t f = 0; f < c.n_frames; ++f) k.l_frame[f] = c.cams[f].pos[1];
   return k;
@@ -234,7 +236,8 @@ bool sampler_key_equal(const curvis_ctx::SamplerKey &a, const curvis_ctx::Sample
   if (a.metric.kind != b.metric.kind || !same(a.metric.rho, b.metric.rho) || !same(a.metric.m, b.metric.m) || !same(a.metric.a, b.metric.a))
     return false;
   if (a.n_frames != b.n_frames || a.max_iter != b.max_iter || a.alpha_nums != b.alpha_nums ||
-      a.max_iterations_sampling != b.max_iterations_sampling || a.fast != b.fast || a.speculate != b.speculate || a.step_scale != b.step_scale)
+      a.max_iterations_sampling != b.max_iterations_sampling || a.fast != b.fast || a.speculate != b.speculate || a.step_scale != b.step_scale ||
+      a.integrator != b.integrator)
     return false;
   if (!same(a.max_radius, b.max_radius) || !same(a.delta, b.delta) || !same(a.thr1, b.thr1) || !same(a.thr2, b.thr2)) return false;
   return a.l_frame.size() == b.l_frame.size() &&
@@ -353,7 +356,8 @@ int sampler_submit(curvis_ctx *ctx, unsigned slot, hipStream_t stream, const Eff
       constexpr bool FAST = decltype(F)::value;
       if constexpr (FAST) /* option "step_scale": the fast step only */
         if (c.adapt) {
-          hipLaunchKernelGGL((sampler_kernel<KIND, true, 1>), dim3(SP.n_jobs), dim3(kSamplerThreads), 0, stream, SP);
+          if (c.adapt == 2) hipLaunchKernelGGL((sampler_kernel<KIND, true, 2>), dim3(SP.n_jobs), dim3(kSamplerThreads), 0, stream, SP);
+          else hipLaunchKernelGGL((sampler_kernel<KIND, true, 1>), dim3(SP.n_jobs), dim3(kSamplerThreads), 0, stream, SP);
           return;
         }
       hipLaunchKernelGGL((sampler_kernel<KIND, FAST>), dim3(SP.n_jobs), dim3(kSamplerThreads), 0, stream, static_cast<const SamplerParams &>(SP));
@@ -377,7 +381,7 @@ int prefetch_efficient_impl(curvis_ctx *ctx, const EfficientCall &call) {
   if (!ctx) return CURVIS_E_INVALID;
   if (!call.metric || !call.cams || call.n_frames == 0) return fail(ctx, CURVIS_E_INVALID, "null metric/camera or zero frames");
   EfficientCall c = call;
-  if (int rc = step_scale_kappa(ctx, c.delta, c.kappa, c.adapt)) return rc; /* option "step_scale": part of what the job is */
+  if (int rc = step_scale_kappa(ctx, c.delta, c.kappa, c.adapt)) return rc; /* options "step_scale" and "integrator": part of what the job is */
   int rc = curvis_metric_validate(c.metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   /* not a case for the device sampler, or (alpha_nums < 3) one that at most runs one round: the render call samples itself */
@@ -1003,7 +1007,7 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, shape.projection, shape.adapt, [&](auto S) {
     using T = decltype(S);
     const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
-    if constexpr (T::ADAPT != 0) hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, 1>), grid, dim3(256), 0, ctx->stream, P);
+    if constexpr (T::ADAPT != 0) hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, P);
     else hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, static_cast<const DirectParams &>(P));
   });
   HIP_TRY(ctx, hipGetLastError());

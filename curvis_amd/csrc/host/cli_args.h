@@ -20,11 +20,13 @@ struct Args {
   int sky_filter = 0; /* sky lookup (library option "sky_filter"): 0 nearest texel, 1 bilinear */
   int projection = 0; /* pixel -> direction (library option "projection"): 0 perspective, 1 equirectangular, 2 fisheye */
   long long step_scale = 0; /* --step-scale L0 as library option "step_scale" = 256 L0: 0 off, else the Euler step grows as |l| / L0 outside L0 */
+  int integrator = 0; /* --integrator euler|heun (library option "integrator"): 0 forward Euler, 1 Heun's method, two Euler steps averaged */
 };
 int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
 int g_sky_filter = 0;  /* Args::sky_filter, likewise */
 int g_projection = 0;  /* Args::projection, likewise */
 long long g_step_scale = 0; /* Args::step_scale, likewise */
+int g_integrator = 0;  /* Args::integrator, likewise */
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(code);
@@ -39,7 +41,8 @@ void usage() {
       "  extensions: [--mode efficient|brute|direct] [--device N] [--devices N] [--batch B] [--stats FILE]\n"
       "              [--sky-broadcast rccl|upload] [--writers T] [--resume] [--png-level -1..9] [--gpu-png auto|on|off]\n"
       "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n"
-      "              [--projection perspective|equirectangular|fisheye] [--step-scale L0]\n");
+      "              [--projection perspective|equirectangular|fisheye] [--step-scale L0]\n"
+      "              [--integrator euler|heun]\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -110,6 +113,11 @@ Args parse_args(int argc, char **argv) {
       if (!decimal || *end != '\0' || !(scaled >= 0.0) || scaled > 1048576.0 || scaled != (double)(long long)scaled)
         die("error: --step-scale must be 0 or a multiple of 1/256 up to 4096", 2);
       a.step_scale = g_step_scale = (long long)scaled;
+    }
+    else if (key == "--integrator") {
+      take(val);
+      if (val != "euler" && val != "heun") die("error: --integrator must be euler or heun", 2);
+      a.integrator = g_integrator = val == "heun" ? 1 : 0;
     }
     else if (key == "-h" || key == "--help") { usage(); std::exit(0); }
     else if (!s.empty() && s[0] == '-') die("error: unexpected argument '" + s + "' found", 2);
@@ -261,6 +269,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
   if (g_sky_filter != 0) check(curvis_ctx_set_option(ctx, "sky_filter", g_sky_filter), ctx, what);
   if (g_projection != 0) check(curvis_ctx_set_option(ctx, "projection", g_projection), ctx, what);
   if (g_step_scale != 0) check(curvis_ctx_set_option(ctx, "step_scale", g_step_scale), ctx, what);
+  if (g_integrator != 0) check(curvis_ctx_set_option(ctx, "integrator", g_integrator), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {

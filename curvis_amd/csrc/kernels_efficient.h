@@ -28,7 +28,8 @@ struct EscapeAngleParamsAdapt : EscapeAngleParams {
 
 /* compute_escape_angle (src/systems.rs:203-261) for ONE alpha on one lane: photon at (0, l, pi/2, 0) with tangent direction
  * (cos a, 0, sin a), Euler loop WITH phi, world direction, angle.  Every lane of the wave that is active here must have entered
- * together (the step counter is wave-uniform).  ADAPT: option "step_scale" != 0, every step takes step_delta(delta, kappa, l). */
+ * together (the step counter is wave-uniform).  ADAPT: 1 option "step_scale" != 0, every step takes step_delta(delta, kappa, l);
+ * 2 option "integrator" = 1, every step is a Heun step with that delta_k (kernels_geodesic.h heun_step). */
 template <int KIND, bool FAST, int ADAPT = 0>
 __device__ __forceinline__ void escape_angle_lane(const cvk::MetricParams &M, double alpha, double l_cam, unsigned max_iter, double max_radius,
                                                   double delta, int fast_ok, double &angle, double &space, unsigned &steps_out, int &status,
@@ -48,7 +49,8 @@ __device__ __forceinline__ void escape_angle_lane(const cvk::MetricParams &M, do
     unsigned k = 0;
     for (;;) {
       ++k;
-      if constexpr (ADAPT != 0) one_step<KIND, true, FAST, true>(M, cvk::step_delta(delta, kappa, q.l), q, lane_ok);
+      if constexpr (ADAPT == 2) heun_step<KIND, true, FAST, true>(M, cvk::step_delta(delta, kappa, q.l), q, lane_ok);
+      else if constexpr (ADAPT != 0) one_step<KIND, true, FAST, true>(M, cvk::step_delta(delta, kappa, q.l), q, lane_ok);
       else one_step<KIND, true, FAST, true>(M, delta, q, lane_ok); /* equatorial photons: see ray_step_fast */
       const bool esc = ray_escaped(q.l, max_radius);
       const unsigned long long em = __builtin_amdgcn_ballot_w64(esc);
@@ -91,7 +93,7 @@ __global__ __launch_bounds__(64) void escape_angle_kernel(const std::conditional
   unsigned steps;
   int status;
   if constexpr (ADAPT != 0)
-    escape_angle_lane<KIND, FAST, 1>(M, P.alpha[i], P.l_cam[i], P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status, P.kappa);
+    escape_angle_lane<KIND, FAST, ADAPT>(M, P.alpha[i], P.l_cam[i], P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status, P.kappa);
   else
     escape_angle_lane<KIND, FAST>(M, P.alpha[i], P.l_cam[i], P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status);
   P.angle[i] = angle;
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(kSamplerThreads) void sampler_kernel(const std::con
           unsigned steps;
           int status;
           if constexpr (ADAPT != 0)
-            escape_angle_lane<KIND, FAST, 1>(M, S.eval_a[k], l_cam, P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status, P.kappa);
+            escape_angle_lane<KIND, FAST, ADAPT>(M, S.eval_a[k], l_cam, P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status, P.kappa);
           else
             escape_angle_lane<KIND, FAST>(M, S.eval_a[k], l_cam, P.max_iter, P.max_radius, P.delta, P.fast_ok, angle, space, steps, status);
           const unsigned slot = S.eval_slot[k];
@@ -484,7 +486,7 @@ struct DirectParamsAdapt : DirectParams { /* the ADAPT instantiations' argument:
 };
 
 /* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
-template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter", PROJ: option "projection", ADAPT: option "step_scale" */
+template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter", PROJ: option "projection", ADAPT: options "step_scale" (1) and "integrator" (2) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 4 : 6)))
 void direct_kernel(const std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams> P) {
   [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */
@@ -510,7 +512,8 @@ void direct_kernel(const std::conditional_t<ADAPT != 0, DirectParamsAdapt, Direc
     int code = cvk::CODE_NONE;
     /* a per-lane loop (lanes outside the frame are idle from the start, so the counter is not wave-uniform) */
     for (unsigned k = 0; k < P.max_iter; ++k) {
-      if constexpr (ADAPT != 0) one_step<KIND, true, FAST, true>(M, cvk::step_delta(P.delta, P.kappa, q.l), q, lane_ok);
+      if constexpr (ADAPT == 2) heun_step<KIND, true, FAST, true>(M, cvk::step_delta(P.delta, P.kappa, q.l), q, lane_ok);
+      else if constexpr (ADAPT != 0) one_step<KIND, true, FAST, true>(M, cvk::step_delta(P.delta, P.kappa, q.l), q, lane_ok);
       else one_step<KIND, true, FAST, true>(M, P.delta, q, lane_ok);
       ++steps;
       if (ray_escaped(q.l, P.max_radius)) {

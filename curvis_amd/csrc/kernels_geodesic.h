@@ -36,7 +36,7 @@ struct IntegrateParams {
    * XCC_ID}; null in normal operation */
   unsigned long long *trace;
 };
-/* The argument of the ADAPT instantiations (option "step_scale", cv_device.h step_delta): IntegrateParams with two members appended.
+/* The argument of the ADAPT instantiations (options "step_scale" and "integrator", cv_device.h step_delta): IntegrateParams with two members appended.
  * The other kernels keep IntegrateParams itself, so not one of their argument loads moves -- the hidden arguments behind the struct
  * (workgroup size) included.  kappa = RN(delta / L0); t_out: the debug dump's x[0] per pixel, integrated on the device (the host's
  * replay_debug_time assumes one delta). */
@@ -146,6 +146,12 @@ __device__ __forceinline__ void one_step(const cvk::MetricParams &M, double delt
     cvk::ray_step<KIND, PHI, MathTablesLds<KIND>::WIDE_SC>(M, q, delta);
 }
 
+/* option "integrator" = 1: one Heun step (cv_device.h ray_step_heun), two of the above from a saved state and an average */
+template <int KIND, bool PHI, bool FAST, bool EQ = false>
+__device__ __forceinline__ void heun_step(const cvk::MetricParams &M, double delta, cvk::Ray &q, bool lane_ok) {
+  cvk::ray_step_heun<KIND, PHI, FAST, MathTablesLds<KIND>::WIDE_SC, EQ>(M, q, delta, lane_ok);
+}
+
 /* final photon -> tangent direction -> nearest sky texel (rows R9-R10 of SURVEY.md 8a); FILTER: the bilinear blend instead */
 template <int KIND, int FILTER = 0>
 __device__ __forceinline__ unsigned shade_ray(const cvk::MetricParams &M, const cvk::SkyParams *sky, const cvk::Ray &q,
@@ -244,9 +250,11 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
 template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter" (FUSED only);
   PROJ: 0 the reference's perspective mapping, 1 option "projection" != 0 (P.projection says which; FUSED only);
   ADAPT: 1 option "step_scale" != 0: every step takes cv_device.h step_delta(P.delta, P.kappa, l) instead of P.delta (the fused kernels and
-  the debug dump's staged PHI kernel, fast step only) */
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7)))
-void geodesic_static(const IntegrateArgs<ADAPT> P) {
+  the debug dump's staged PHI kernel, fast step only); 2 option "integrator" = 1: a step is cv_device.h ray_step_heun with that delta_k
+  (kappa = +0 while "step_scale" is off: step_delta then returns P.delta for every l) */
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7) - (ADAPT == 2 ? 1 : 0))))
+void geodesic_static(const IntegrateArgs<ADAPT> P) { /* the Heun step holds the saved state across two stages, four register pairs more:
+  at 7 (5) waves the loop would spill them, so the ADAPT = 2 kernels ask for one wave less */
   static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");
   static_assert(FILTER == 0 || (FUSED && !PHI), "the filtered lookup exists in the fused epilogues only");
   static_assert(PROJ == 0 || (FUSED && !PHI), "the projections exist in the fused kernels only");
@@ -285,8 +293,13 @@ void geodesic_static(const IntegrateArgs<ADAPT> P) {
       ++k;
       if constexpr (ADAPT != 0) {
         const double dk = cvk::step_delta(P.delta, P.kappa, q.l);
-        one_step<KIND, PHI, FAST>(M, dk, q, lane_ok_w);
-        if constexpr (PHI) t = t + (1.0 * -1.0) * dk;
+        if constexpr (ADAPT == 2) {
+          heun_step<KIND, PHI, FAST>(M, dk, q, lane_ok_w);
+          if constexpr (PHI) t = cvk::heun_time(t, dk);
+        } else {
+          one_step<KIND, PHI, FAST>(M, dk, q, lane_ok_w);
+          if constexpr (PHI) t = t + (1.0 * -1.0) * dk;
+        }
       } else {
         one_step<KIND, PHI, FAST>(M, P.delta, q, lane_ok_w);
       }

@@ -106,6 +106,8 @@ struct curvis_ctx {
                                direction, defined in include/curvis_hip.h (cv_device.h sky_bilinear_taps / sky_bilinear_blend) */
   int projection = 0;       /* 0: the reference's perspective camera; 1: equirectangular; 2: equidistant fisheye -- pixel -> camera-space
                                vector, defined in include/curvis_hip.h (cv_device.h camera_pixel_vector) */
+  int integrator = 0;       /* 0: forward Euler, the reference's loop; 1: Heun's method composed of two Euler steps -- defined in
+                               include/curvis_hip.h (cv_device.h ray_step_heun) */
   int64_t step_scale = 0;   /* S in [0, 2^20]; 0: every Euler step takes the call's delta (the reference).  S != 0: L0 = S / 256, and a step
                                from radial coordinate l takes max(delta, |l| delta / L0) -- defined in include/curvis_hip.h (cv_device.h
                                step_delta) */
@@ -127,6 +129,7 @@ struct curvis_ctx {
     double max_radius = 0, delta = 0, thr1 = 0, thr2 = 0;
     int fast = 0, speculate = 0;
     int64_t step_scale = 0; /* option "step_scale": other steps, other tables */
+    int integrator = 0;     /* option "integrator": likewise */
     std::vector<double> l_frame; /* radial coordinate of every frame's camera */
   };
   struct SamplerSlot {
@@ -198,9 +201,10 @@ struct LaunchShape {
   static constexpr int KIND = KIND_, SS = SS_, FILTER = FILTER_, PROJ = PROJ_, ADAPT = ADAPT_;
   static constexpr bool FAST = FAST_;
 };
-/* adapt: option "step_scale" != 0 (ADAPT = 1 exists for the fast step only: prepare_call_shape refuses the option with fast_math = 0) */
+/* adapt: 0, 1 option "step_scale" != 0 under the Euler step, 2 option "integrator" = 1 (ADAPT != 0 exists for the fast step only:
+ * prepare_call_shape refuses both options with fast_math = 0) */
 template <typename F>
-auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, uint32_t projection, bool adapt, F &&f) {
+auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, uint32_t projection, int adapt, F &&f) {
   return with_kind(kind, [&](auto K) {
     return with_flag(fast, [&](auto A) {
       auto with_ss = [&](auto N) {
@@ -208,8 +212,12 @@ auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, uint32
         constexpr bool FAST = decltype(A)::value;
         if constexpr (FAST)
           if (adapt) {
-            if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1, 1>{});
-            return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0, 1>{});
+            auto with_adapt = [&](auto D) {
+              constexpr int ADAPT = decltype(D)::value;
+              if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1, ADAPT>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1, ADAPT>{});
+              return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0, ADAPT>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0, ADAPT>{});
+            };
+            return adapt == 2 ? with_adapt(std::integral_constant<int, 2>{}) : with_adapt(std::integral_constant<int, 1>{});
           }
         if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1>{});
         return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0>{});
@@ -233,20 +241,28 @@ constexpr uint32_t kSkyFilterMaxSide = 1u << 23;
  * of it is pixel (x, y) of the original, cv_device.h ray_init). */
 struct CallShape {
   uint32_t ss = 1, filter = 0, projection = 0;
-  double kappa = 0.0; /* option "step_scale" != 0: RN(delta / L0), else 0 (never read) */
-  bool adapt = false; /* option "step_scale" != 0 */
+  double kappa = 0.0; /* option "step_scale" != 0: RN(delta / L0), else +0 (read under "integrator" = 1 only: step_delta then gives delta) */
+  int adapt = 0;      /* the kernels' ADAPT: 2 option "integrator" = 1, else 1 option "step_scale" != 0, else 0 */
   std::vector<curvis_camera> fine;
 };
 /* Option "step_scale" for a call with step delta: off (adapt = false), or kappa = RN(delta / L0) with L0 = S / 256 (exact), one IEEE
  * division, here and nowhere else.  The option needs a positive delta and the fast step (the strict step exists for the theorem about
  * the reference's own frames, and has no ADAPT kernels). */
-int step_scale_kappa(curvis_ctx *ctx, double delta, double &kappa, bool &adapt) {
+int step_scale_kappa(curvis_ctx *ctx, double delta, double &kappa, int &adapt) {
   kappa = 0.0;
-  adapt = ctx->step_scale != 0;
+  adapt = ctx->integrator != 0 ? 2 : ctx->step_scale != 0 ? 1 : 0;
   if (!adapt) return CURVIS_OK;
-  if (!(delta > 0.0)) return fail(ctx, CURVIS_E_INVALID, "step_scale != 0: the step delta must be greater than 0");
-  if (ctx->fast_math == 0) return fail(ctx, CURVIS_E_INVALID, "step_scale != 0: fast_math = 0 (the strict step) takes the reference's fixed step only (set step_scale = 0)");
-  kappa = cvk::step_kappa(delta, ctx->step_scale);
+  /* Option "integrator" = 1 (Heun) has the same two needs, for the same reasons, and is refused under its own name while "step_scale"
+   * is off.  Its kernels are the ADAPT = 2 ones, which take delta_k from step_delta whether or not the steps are scaled: with kappa = +0,
+   * |l| kappa is 0 or NaN and the maximum with delta > 0 is delta, for every l. */
+  if (!(delta > 0.0))
+    return fail(ctx, CURVIS_E_INVALID, ctx->step_scale != 0 ? "step_scale != 0: the step delta must be greater than 0"
+                                                            : "integrator = 1: the step delta must be greater than 0");
+  if (ctx->fast_math == 0)
+    return fail(ctx, CURVIS_E_INVALID,
+                ctx->step_scale != 0 ? "step_scale != 0: fast_math = 0 (the strict step) takes the reference's fixed step only (set step_scale = 0)"
+                                     : "integrator = 1: fast_math = 0 (the strict step) takes the reference's Euler step only (set integrator = 0)");
+  if (ctx->step_scale != 0) kappa = cvk::step_kappa(delta, ctx->step_scale);
   return CURVIS_OK;
 }
 /* cams: the caller's n_frames cameras on entry, those the kernels run over on return (s.fine with ss > 1).  With the filter on, both
@@ -490,14 +506,14 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
 template <int KIND, bool PHI, bool FAST, int SS, int FILTER, int PROJ, int ADAPT = 0>
 int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused, int relay) {
   const IntegrateParams &P = PA; /* what every kernel but the ADAPT ones takes */
-  if constexpr (ADAPT == 0) /* scaled steps never take the relay kernel (choose_render_path) */
+  if constexpr (ADAPT == 0) /* scaled steps and Heun steps never take the relay kernel (choose_render_path) */
     if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, P, relay == 2);
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const dim3 grid((unsigned)((P.total_rays + bt - 1ull) / bt));
   bool staged = false; /* launched a kernel that leaves the shading to shade_kernel */
   if constexpr (ADAPT != 0) { /* the fused kernel, or the debug dump's staged one; render_impl refuses every other shape */
     if constexpr (PHI) {
-      hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, false, 1, 0, 0, 1>), grid, dim3(bt), 0, ctx->stream, PA);
+      hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, false, 1, 0, 0, ADAPT>), grid, dim3(bt), 0, ctx->stream, PA);
       staged = true;
     }
   } else if constexpr (SS == 1 && FILTER == 0 && PROJ == 0) {
@@ -518,7 +534,7 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused
       staged = true;
     }
   }
-  if constexpr (ADAPT != 0 && !PHI) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ, 1>), grid, dim3(bt), 0, ctx->stream, PA);
+  if constexpr (ADAPT != 0 && !PHI) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ, ADAPT>), grid, dim3(bt), 0, ctx->stream, PA);
   if constexpr (ADAPT == 0)
     if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ>), grid, dim3(bt), 0, ctx->stream, P);
   HIP_TRY(ctx, hipGetLastError());
@@ -527,7 +543,7 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused
 
 /* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled, never filtered and always in perspective */
 int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParamsAdapt &P, uint32_t ss,
-                         uint32_t filter, bool adapt) {
+                         uint32_t filter, int adapt) {
   return with_launch_shape(kind, fast, ss, filter, (uint32_t)P.projection, adapt, [&](auto S) {
     using T = decltype(S);
     if constexpr (T::SS == 1 && T::FILTER == 0 && T::PROJ == 0)
@@ -579,7 +595,7 @@ struct BruteCall {
   uint32_t filter;               /* option "sky_filter" for this call */
   uint32_t projection;           /* option "projection" for this call */
   double kappa = 0.0;            /* option "step_scale" for this call: RN(delta / L0) ... */
-  bool adapt = false;            /* ... and whether it is on */
+  int adapt = 0;                 /* ... and the kernels' ADAPT (CallShape) */
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
   size_t npix = 0, fb_bytes = 0;
 };
@@ -615,7 +631,7 @@ RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
                                                                    : 4ull * (unsigned long long)ctx->prop.multiProcessorCount;
   const size_t relay_staging = (size_t)tiles * 64u * kStoreBytesPerPixel;
   /* option "step_scale": the static kernel -- the relay segments are sized in fixed-delta steps and its hand-over pattern was tuned on
-   * fixed-delta step counts */
+   * fixed-delta step counts.  Option "integrator" = 1 likewise: there is no relay form of the Heun step */
   p.relay = !c.adapt && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
             relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
   p.chunk = c.n_frames;
@@ -959,32 +975,37 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
   BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u, 0u};
-  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->projection && !ctx->step_scale)) return render_rays(ctx, c);
+  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->projection && !ctx->step_scale && !ctx->integrator)) return render_rays(ctx, c);
   /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under
    * the name of the projection when it is on, else of the filter when that is on, else of the supersampling when that is on.  The scaled
    * steps (option "step_scale") exist in the fused kernels and in the debug dump's: a shape with a message of its own in the last
    * column is refused under the option's name when none of the other three refuses it.  The option's fourth refusal, fast_math = 0,
-   * holds for all three renderers and is therefore made where they all pass, in step_scale_kappa (prepare_call_shape). */
-  const bool f = ctx->sky_filter != 0, p = ctx->projection != 0, n = ctx->supersample > 1, a = ctx->step_scale != 0;
+   * holds for all three renderers and is therefore made where they all pass, in step_scale_kappa (prepare_call_shape).  The Heun step
+   * (option "integrator" = 1) exists in the same kernels as the scaled steps and is refused for the same shapes, under its own name
+   * when "step_scale" is off. */
+  const bool f = ctx->sky_filter != 0, p = ctx->projection != 0, n = ctx->supersample > 1, a = ctx->step_scale != 0, h = ctx->integrator != 0;
   const struct {
     bool refused;
-    const char *projection, *filter, *supersample, *step_scale;
+    const char *projection, *filter, *supersample, *step_scale, *integrator;
   } shapes[3] = {
       {dbg_out != nullptr, "projection != 0: the debug dump replays the perspective camera (set projection = 0)",
        "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)",
-       "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)", nullptr},
+       "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)", nullptr, nullptr},
       {ctx->variant == 0, "projection != 0: variant = 0 (the persistent kernel) has the perspective camera only",
        "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
        "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve",
-       "step_scale != 0: variant = 0 (the persistent kernel) takes the reference's fixed step only"},
+       "step_scale != 0: variant = 0 (the persistent kernel) takes the reference's fixed step only",
+       "integrator = 1: variant = 0 (the persistent kernel) takes the reference's Euler step only"},
       {ctx->fuse_shade == 0, "projection != 0: fuse_shade = 0 (the unfused static kernel) has the perspective camera only",
        "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
        "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve",
-       dbg_out ? nullptr : "step_scale != 0: fuse_shade = 0 (the unfused static kernel) takes the reference's fixed step only outside the debug dump"}};
+       dbg_out ? nullptr : "step_scale != 0: fuse_shade = 0 (the unfused static kernel) takes the reference's fixed step only outside the debug dump",
+       dbg_out ? nullptr : "integrator = 1: fuse_shade = 0 (the unfused static kernel) takes the reference's Euler step only outside the debug dump"}};
   for (const auto &s : shapes)
     if (s.refused) {
       const char *why = p ? s.projection : f ? s.filter : n ? s.supersample : nullptr;
       if (!why && a) why = s.step_scale;
+      if (!why && h) why = s.integrator;
       if (why) return fail(ctx, CURVIS_E_INVALID, why);
     }
   CallShape shape;

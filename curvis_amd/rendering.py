@@ -134,14 +134,17 @@ class ImageRenderingSystem:
     traces N x N rays per pixel and averages them on the device; sky_filter="bilinear" (not in the reference; "nearest" is its
     lookup) blends the four sky texels around every ray's direction; projection="equirectangular" or "fisheye" (not in the reference;
     "perspective" is its camera) renders a 360-degree or a dome frame (library option "projection"); step_scale=L0 (not in the
-    reference; 0 is its fixed step) lets the Euler step grow as |l| / L0 outside the distance L0 (library option "step_scale")."""
+    reference; 0 is its fixed step) lets the Euler step grow as |l| / L0 outside the distance L0 (library option "step_scale"); integrator="heun" (not in the
+    reference; "euler" is its loop) integrates with Heun's method, two Euler steps averaged (library option "integrator")."""
 
     def __init__(self, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-                 projection="perspective", step_scale=0.0):
+                 projection="perspective", step_scale=0.0, integrator="euler"):
         from .images import load_image_as_spherical_image
-        from .systems import RelativisticSystem, check_projection, check_sky_filter, check_step_scale, check_supersample
+        from .systems import RelativisticSystem, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
         check_step_scale(step_scale)
         self.step_scale = step_scale
+        check_integrator(integrator)
+        self.integrator = integrator
         self.supersample = check_supersample(supersample)
         check_sky_filter(sky_filter)
         self.sky_filter = sky_filter
@@ -157,10 +160,10 @@ class ImageRenderingSystem:
 
     @classmethod
     def new(cls, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-            projection="perspective", step_scale=0.0):
+            projection="perspective", step_scale=0.0, integrator="euler"):
         """ImageRenderingSystem::new(metric, image_rendering_settings) (src/rendering.rs:33-70)"""
         return cls(metric, image_rendering_settings, context=context, mode=mode, supersample=supersample, sky_filter=sky_filter,
-                   projection=projection, step_scale=step_scale)
+                   projection=projection, step_scale=step_scale, integrator=integrator)
 
     def render(self):
         import os
@@ -175,12 +178,14 @@ class ImageRenderingSystem:
         if self.mode == "brute":
             image = self.relativistic_system.render_image(st.max_iterations_propagation, st.escape_radius, st.ray_integration_step,
                                                           supersample=self.supersample, sky_filter=self.sky_filter,
-                                                          projection=self.projection, step_scale=self.step_scale)
+                                                          projection=self.projection, step_scale=self.step_scale,
+                                                          integrator=self.integrator)
         else:
             image = self.relativistic_system.render_image_efficient(
                 st.max_iterations_propagation, st.escape_radius, st.ray_integration_step, st.alphas_num,
                 st.max_iterations_sampling, st.sampling_convergence_threshold_1, st.sampling_convergence_threshold_2,
-                supersample=self.supersample, sky_filter=self.sky_filter, projection=self.projection, step_scale=self.step_scale)
+                supersample=self.supersample, sky_filter=self.sky_filter, projection=self.projection, step_scale=self.step_scale,
+                integrator=self.integrator)
         path_of_image = os.path.join(folder, os.path.splitext(st.output_image_name)[0] + ".png")
         save_image(path_of_image, image)
         return path_of_image
@@ -209,15 +214,18 @@ class VideoRenderingSystem:
     and downloads keep `resolution`, the per-frame statistics count the N x N times as many rays.  sky_filter="bilinear" (not in
     the reference; "nearest" is its lookup) blends the four sky texels around every ray's direction.  projection="equirectangular" or
     "fisheye" (not in the reference; "perspective" is its camera): library option "projection" on every frame.  step_scale=L0 (not in
-    the reference; 0 is its fixed step): library option "step_scale" on every frame."""
+    the reference; 0 is its fixed step): library option "step_scale" on every frame.  integrator="heun" (not in the reference;
+    "euler" is its loop): library option "integrator" on every frame, the prefetch included."""
 
     def __init__(self, metric, context, interpolator, frame_rate, resolution, camera_diagonal, camera_focal_length,
                  escape_radius, max_iterations_propagation, ray_integration_step, rank=0, world_size=1, batch=8,
                  mode="efficient", sampling_initial_nums=100, sampling_convergence_threshold_1=1e-5, supersample=1,
-                 sky_filter="nearest", projection="perspective", step_scale=0.0):
-        from .systems import check_projection, check_sky_filter, check_step_scale, check_supersample
+                 sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler"):
+        from .systems import check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
         self._step_scale = check_step_scale(step_scale)
         self.step_scale = step_scale
+        self._integrator = check_integrator(integrator)
+        self.integrator = integrator
         if mode not in ("efficient", "brute"):
             raise ValueError("mode must be 'efficient' or 'brute'")
         self.supersample = check_supersample(supersample)
@@ -242,15 +250,16 @@ class VideoRenderingSystem:
 
     @classmethod
     def new(cls, metric, video_rendering_settings, context=None, rank=0, world_size=1, batch=8, mode="efficient", supersample=1,
-            sky_filter="nearest", projection="perspective", step_scale=0.0):
+            sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler"):
         """VideoRenderingSystem::new(metric, video_rendering_settings) (src/rendering.rs:188-221): loads the two
         backgrounds into the context's HBM and the camera path into an Interpolator.  The reference passes
         `alphas_num` and `max_iterations_sampling` separately and `sampling_convergence_threshold_1` twice (:299-307);
         so does this (threshold_2 of the settings is never read, as there)."""
         from .images import load_image_as_spherical_image
-        from .systems import check_projection, check_sky_filter, check_step_scale, check_supersample, default_context
+        from .systems import check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context
         check_supersample(supersample)  # before the context and the files are touched
         check_step_scale(step_scale)
+        check_integrator(integrator)
         check_sky_filter(sky_filter)
         check_projection(projection)
         st = video_rendering_settings
@@ -262,7 +271,7 @@ class VideoRenderingSystem:
                    st.max_iterations_propagation, st.ray_integration_step, rank=rank, world_size=world_size, batch=batch,
                    mode=mode, sampling_initial_nums=st.alphas_num,
                    sampling_convergence_threshold_1=st.sampling_convergence_threshold_1, supersample=supersample,
-                   sky_filter=sky_filter, projection=projection, step_scale=step_scale)
+                   sky_filter=sky_filter, projection=projection, step_scale=step_scale, integrator=integrator)
         self.max_iterations_sampling = int(st.max_iterations_sampling)
         self.video_rendering_settings = st
         return self
@@ -318,10 +327,10 @@ class VideoRenderingSystem:
 
     def _render_batch(self, cams, download):
         if (getattr(self, "supersample", 1) != 1 or getattr(self, "_sky_filter", 0) != 0 or getattr(self, "_projection", 0) != 0
-                or getattr(self, "_step_scale", 0) != 0):
+                or getattr(self, "_step_scale", 0) != 0 or getattr(self, "_integrator", 0) != 0):
             from .systems import _Supersampled
             with _Supersampled(self.context, getattr(self, "supersample", 1), getattr(self, "_sky_filter", 0),
-                               getattr(self, "_projection", 0), getattr(self, "_step_scale", 0)):
+                               getattr(self, "_projection", 0), getattr(self, "_step_scale", 0), getattr(self, "_integrator", 0)):
                 return self._render_batch_as_set(cams, download)
         return self._render_batch_as_set(cams, download)
 
@@ -342,11 +351,12 @@ class VideoRenderingSystem:
             thr1 = self.sampling_convergence_threshold_1
             args = (self.metric, cams, self.max_iterations_propagation, self.escape_radius, self.ray_integration_step,
                     self.sampling_initial_nums, getattr(self, "max_iterations_sampling", self.sampling_initial_nums), thr1, thr1)
-            if getattr(self, "_step_scale", 0) != 0:
-                # "step_scale" is part of what identifies a sampler job: a prefetch made under another value is never consumed
+            if getattr(self, "_step_scale", 0) != 0 or getattr(self, "_integrator", 0) != 0:
+                # "step_scale" and "integrator" are part of what identifies a sampler job: a prefetch made under another value is
+                # never consumed
                 from .systems import _Supersampled
                 with _Supersampled(self.context, getattr(self, "supersample", 1), getattr(self, "_sky_filter", 0),
-                                   getattr(self, "_projection", 0), self._step_scale):
+                                   getattr(self, "_projection", 0), getattr(self, "_step_scale", 0), getattr(self, "_integrator", 0)):
                     self.context.prefetch_efficient(*args)
             else:
                 self.context.prefetch_efficient(*args)

@@ -792,13 +792,24 @@ def check_step_scale(step_scale):
     return int(scaled)
 
 
+INTEGRATORS = ("euler", "heun")  # the values of library option "integrator", 0 and 1
+
+
+def check_integrator(integrator):
+    """the integrator as the library option's value, or ValueError: "euler" (0, the reference's) or "heun" (1)"""
+    if not isinstance(integrator, str) or integrator not in INTEGRATORS:
+        raise ValueError("integrator must be 'euler' or 'heun'")
+    return INTEGRATORS.index(integrator)
+
+
 class _Supersampled:
     """the context's "supersample" option set to `factor` -- and "sky_filter" to `sky_filter` (0 or 1), "projection" to `projection`
-    (0, 1 or 2), "step_scale" to `step_scale` (the integer S) -- for the duration of a render call, then put back"""
+    (0, 1 or 2), "step_scale" to `step_scale` (the integer S), "integrator" to `integrator` (0 or 1) -- for the duration of a render
+    call, then put back"""
 
-    def __init__(self, context, factor, sky_filter=0, projection=0, step_scale=0):
+    def __init__(self, context, factor, sky_filter=0, projection=0, step_scale=0, integrator=0):
         self.context, self.want = context, (("supersample", factor), ("sky_filter", sky_filter), ("projection", projection),
-                                            ("step_scale", step_scale))
+                                            ("step_scale", step_scale), ("integrator", integrator))
 
     def __enter__(self):
         self.before = [self.context.get_option(key) for key, _ in self.want]
@@ -819,7 +830,9 @@ class RelativisticSystem:
     reference's lookup) or "bilinear" (not in the reference: the four texels around a ray's direction, blended on the device); and
     projection="perspective" (the reference's camera), "equirectangular" or "fisheye" (not in the reference: library option
     "projection"); and step_scale=L0 (not in the reference; 0, the default, is its fixed step): outside the coordinate distance L0, a
-    multiple of 1/256, a ray's Euler step grows as |l| / L0 (library option "step_scale")."""
+    multiple of 1/256, a ray's Euler step grows as |l| / L0 (library option "step_scale"); and integrator="euler" (the reference's
+    forward Euler) or "heun" (not in the reference: Heun's method, second order, two Euler steps averaged; library option
+    "integrator")."""
 
     def __init__(self, metric, background_positive, background_negative, camera, context=None):
         self.metric = metric
@@ -837,12 +850,12 @@ class RelativisticSystem:
             ctx.set_sky(1, self.background_negative)
 
     def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
-                     step_scale=0.0):
+                     step_scale=0.0, integrator="euler"):
         """The per-pixel renderer; returns an HxWx3 uint8 array (DynamicImage::ImageRgb8)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
-        scale = check_step_scale(step_scale)
+        scale, heun = check_step_scale(step_scale), check_integrator(integrator)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun):
             rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
         self.last_stats = st
         return rgb
@@ -850,12 +863,12 @@ class RelativisticSystem:
     def render_image_efficient(self, max_iterations_propagation, max_radius, delta, alpha_nums,
                                max_iterations_sampling, sampling_convergence_threshold_1,
                                sampling_convergence_threshold_2, supersample=1, sky_filter="nearest", projection="perspective",
-                               step_scale=0.0):
+                               step_scale=0.0, integrator="euler"):
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
-        scale = check_step_scale(step_scale)
+        scale, heun = check_step_scale(step_scale), check_integrator(integrator)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun):
             rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
                                                     alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
                                                     sampling_convergence_threshold_2)
@@ -863,13 +876,13 @@ class RelativisticSystem:
         return rgb
 
     def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
-                            step_scale=0.0):
+                            step_scale=0.0, integrator="euler"):
         """NOT in the reference: the image render_image_efficient approximates, with compute_escape_angle evaluated
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
-        scale = check_step_scale(step_scale)
+        scale, heun = check_step_scale(step_scale), check_integrator(integrator)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun):
             rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
         self.last_stats = st
         return rgb

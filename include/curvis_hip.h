@@ -201,6 +201,12 @@ int curvis_update_relativistic_object(const curvis_metric *metric, double x[4], 
  * `out`, and S != 0 with !(delta > 0).  Fed into curvis_update_relativistic_object it walks a ray the way the kernels do. */
 #define CURVIS_STEP_SCALE_MAX (1u << 20)
 int curvis_step_delta(double delta, int64_t step_scale, double l, double *out);
+/* Option "integrator" = 1 (defined with the options below) for ONE step: a Heun step of (x, p_cov) in place, on the host, all eight
+ * components, with the IEEE form of the Euler step (cv_device.h ray_step_heun, the text the kernels' loops call; the fast step
+ * returns the same bits).  x[0] is averaged like the other coordinates; p_cov[0] and p_cov[3] keep their bits.  With `delta` taken
+ * from curvis_step_delta at x[1] it walks a ray the way the kernels do under both options.  Returns as
+ * curvis_update_relativistic_object does. */
+int curvis_heun_step(const curvis_metric *metric, double x[4], double p_cov[4], double delta);
 /* SphericalImage::get_pixel_from_vector3's texel (src/images.rs:115-142, 171-174; src/algebra.rs:106-134) for an image of
  * w x h texels whose inverse orientation is inv_rot (NULL = the default forward x / up z): raw `as u32` indices.
  * Returns CURVIS_OK, or CURVIS_E_INVALID with the indices still set when x == w or y == h (the reference's
@@ -464,6 +470,26 @@ int curvis_ctx_download_wait(curvis_ctx *ctx);
  * "fuse_shade" = 0.  curvis_render_brute_debug is served (when none of the three options above is on).
  * curvis_photon_trajectories, curvis_compute_escape_angles and curvis_update_relativistic_object take their delta explicitly and
  * do not look at the option; curvis_step_delta evaluates step 3 on the host),
+ * "integrator" (0, the default: forward Euler, the reference's loop bit for bit and the kernels that exist without the option; 1: Heun's
+ * method, the explicit trapezoid, second order; anything else is refused with CURVIS_E_INVALID and the old value stays.  With E(y, d)
+ * the reference's update_relativistic_object, y + d/2 (f(y) + f(y + d f(y))) = 1/2 (y + E(E(y, d), d)), so for integrator = 1 step k of
+ * a ray in state y_k = (l, theta, phi, p_l, p_theta):
+ *   1. delta_k is what "step_scale" defines from l_k, the radial coordinate before the step: step_delta(delta, kappa, l_k); with
+ *      "step_scale" = 0 it is delta.  (The code runs one path for both: with kappa = +0, |l| kappa is 0 or NaN and the maximum with
+ *      delta > 0 is delta, for every l.)
+ *   2. y' = E(y_k, delta_k) and y'' = E(y', delta_k): the reference's step, every operation individually rounded in its order -- in
+ *      the kernels the fast step under its contract.  Both stages use the same delta_k; the scale is not re-evaluated at y'.
+ *   3. y_{k+1}[c] = (y_k[c] + y''[c]) * 0.5 for c in {l, theta, p_l, p_theta}, and phi where it is integrated: one IEEE add, then one
+ *      IEEE multiply.  p_phi (and p_t) are constants of the step and are kept, not averaged.  The debug dump's x[0] is averaged the
+ *      same way over t'' = (t + (1.0 * -1.0) delta_k) + (1.0 * -1.0) delta_k.
+ *   4. The escape test |l| > max_radius is made on y_{k+1} only, never on a stage.  max_iterations and the counter `steps` count Heun
+ *      steps; each is two evaluations of the right-hand side.  new_photon, direction, lookup and the other counters are unchanged.
+ * All three renderers honour it (the efficient renderer in both samplers); it combines with "step_scale", "supersample",
+ * "sky_filter" and "projection", row bands, batches and the prefetch, whose jobs it is part of.  With integrator = 1 the brute
+ * renderer launches the static kernel, never the relay kernel.  Refused with CURVIS_E_INVALID while integrator = 1, as under
+ * "step_scale": a render call with !(delta > 0), "fast_math" = 0 (every renderer), "variant" = 0 and, outside the debug dump,
+ * "fuse_shade" = 0.  curvis_render_brute_debug is served.  curvis_photon_trajectories, curvis_compute_escape_angles and
+ * curvis_update_relativistic_object stay the reference's functions; curvis_heun_step evaluates steps 2 and 3 on the host),
  * "max_store_bytes" (ray-store budget that bounds the frames per launch of a batch),
  * "sampling_speculation" (efficient renderer: depth of the speculative dyadic subtree evaluated below every
  * refined interval; 0 = one launch per refinement round; default -1 = automatic, 10 for one or two frames, 6 for three to five and 4
