@@ -78,6 +78,14 @@ SYMBOLS = {
     "curvis_heun_step": (C.c_int, [C.POINTER(Metric), _dp, _dp, C.c_double]),
     "curvis_sky_texel_index": (C.c_int, [C.c_uint32, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "curvis_sky_bilinear_taps": (C.c_int, [C.c_uint32, C.c_uint32, _dp, _dp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "curvis_sky_mip_rho": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, C.POINTER(C.c_uint32), C.c_int32,
+                                     C.POINTER(C.c_uint32)]),
+    "curvis_sky_mip_level": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "curvis_sky_mip_taps": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_uint32)]),
+    "curvis_sky_mip_mix": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "curvis_sky_mip_pyramid": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "curvis_ctx_sky_mip_level": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "curvis_render_brute": (C.c_int, [_vp, C.POINTER(Metric), C.POINTER(CameraC), C.c_uint32, C.c_double, C.c_double,
                                       _vp, C.POINTER(Stats)]),
     "curvis_render_brute_rows": (C.c_int, [_vp, C.POINTER(Metric), C.POINTER(CameraC), C.c_uint32, C.c_uint32, C.c_uint32,
@@ -129,6 +137,7 @@ SYMBOLS = {
     "curvis_selftest_math3": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_size_t]),
     "curvis_selftest_fast_step": (C.c_int, [_vp, C.POINTER(Metric), C.c_double, C.c_double, _dp, C.c_size_t, _dp]),
     "curvis_selftest_sky_indices": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _dp, _dp, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "curvis_selftest_sky_mip": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.c_size_t, _vp]),
     "curvis_selftest_sky_bilinear": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _dp, _vp, _dp, C.c_size_t, C.POINTER(C.c_uint32), _vp]),
 }
 

@@ -40,6 +40,14 @@
  *   the same with a trailing PROJ = 1      option "projection" != 0: the prologues form the pixel's camera-space vector by
  *       cv_device.h camera_pixel_vector's equirectangular or fisheye branch (a scalar branch on a kernel argument; nothing of it
  *       lives into the Euler loop); PROJ = 0 are the kernels above, instruction for instruction.
+ *   the same with FILTER = 2 (geodesic_static, direct_kernel, efficient_pixel_ss_kernel<SS, 2> with SS = 1 included; no relay form)
+ *       option "sky_mipmap" = 1 on top of the filter: the wave exchanges every ray's sky indices inside its 2 x 2 quads and each lane
+ *       blends two levels of the sky's mip chain (kernels_epilogue.h sky_mip_shade); the argument is the FILTER = 1 kernel's with the
+ *       level tables appended.
+ *   efficient_pixel_ss_kernel<1, FILTER>   FILTER = 0, 1: the tile enumeration alone, reached through option "pixel_tiled" = 1 only
+ *       (tools/gpu_sky_mipmap_cost.py times it beside the linear kernel).
+ *   sky_mip_kernel                         one level of a sky's mip chain from the level below it.
+ *   selftest_sky_mip_kernel                the per-ray colour of "sky_mipmap" on the tests' (Xc, Yc, rho).
  *   selftest_sky_bilinear_kernel           the two functions alone, both instantiations, on the tests' directions.
  *   selftest_math_kernel                   cv_math.h / IEEE div / sqrt / hardware seeds for the tests.
  *   selftest_sky_indices_kernel            cvk::sky_indices (direction -> texel), both instantiations, on the tests' directions.
@@ -252,8 +260,14 @@ int curvis_ctx_set_sky_device(curvis_ctx *ctx, int which, const void *dev_rgba, 
     return CURVIS_OK;
   }
   if ((rc = S.allocate(ctx))) return rc;
+  if ((rc = ctx->ev0.ensure(ctx)) || (rc = ctx->ev1.ensure(ctx))) return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream)); /* the copy alone, by HIP events: option "last_sky_copy_us" */
   HIP_TRY(ctx, hipMemcpyAsync(S.texels, dev_rgba, S.bytes(), hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_sky_copy_us = (int64_t)(ms * 1000.0f + 0.5f);
   return CURVIS_OK;
 }
 
@@ -319,6 +333,7 @@ int curvis_ctx_bcast_skies(curvis_ctx *ctx, void *nccl_comm, int root) {
     return fail(ctx, CURVIS_E_NO_SKY, rank == root ? "root rank must hold both skies before the broadcast"
                                                    : "the root rank of the sky broadcast holds no skies");
   const uint32_t *shape = hdr + 1;
+  for (int s = 0; s < 2; ++s) ctx->sky[s].drop_mips(); /* option "sky_mipmap": every device rebuilds its own chain; it is not broadcast */
   for (int s = 0; s < 2; ++s) {
     const uint32_t w = shape[2 * s], h = shape[2 * s + 1];
     const char *stage = s == 0 ? "texture_broadcast(+l sky)" : "texture_broadcast(-l sky)";
@@ -606,6 +621,75 @@ int curvis_sky_bilinear_taps(uint32_t w, uint32_t h, const double inv_rot[9], co
   taps[0] = t.x0, taps[1] = t.x1, taps[2] = t.y0, taps[3] = t.y1, taps[4] = t.fx, taps[5] = t.fy;
   raw[0] = t.tx, raw[1] = t.ty;
   return t.oob ? CURVIS_E_INVALID : CURVIS_OK;
+}
+
+int curvis_sky_mip_rho(uint32_t w, const uint32_t own[2], const uint32_t horizontal[2], int32_t horizontal_ok, const uint32_t vertical[2],
+                       int32_t vertical_ok, uint32_t *rho) {
+  if (!own || !horizontal || !vertical || !rho || w == 0 || w > kSkyFilterMaxSide) return CURVIS_E_INVALID;
+  *rho = cvk::sky_mip_rho(own[0], own[1], w << 8, horizontal[0], horizontal[1], horizontal_ok != 0, vertical[0], vertical[1], vertical_ok != 0);
+  return CURVIS_OK;
+}
+
+int curvis_sky_mip_level(uint32_t rho, uint32_t levels, uint32_t *k, uint32_t *f) {
+  if (!k || !f || levels == 0) return CURVIS_E_INVALID;
+  unsigned kk, ff;
+  cvk::sky_mip_level(rho, levels, kk, ff);
+  *k = kk, *f = ff;
+  return CURVIS_OK;
+}
+
+int curvis_sky_mip_taps(uint32_t w, uint32_t h, uint32_t level, uint32_t xc, uint32_t yc, uint32_t taps[6], uint32_t size[2]) {
+  if (!taps || !size || w == 0 || h == 0 || w > kSkyFilterMaxSide || h > kSkyFilterMaxSide) return CURVIS_E_INVALID;
+  if (level >= cvk::sky_mip_levels(w, h) || xc >= (w << 8) || yc >= (h << 8)) return CURVIS_E_INVALID;
+  unsigned wk = w, hk = h;
+  for (uint32_t k = 0; k < level; ++k) wk = (wk + 1u) >> 1, hk = (hk + 1u) >> 1;
+  cvk::SkyTaps t;
+  cvk::sky_mip_taps(xc >> level, yc >> level, wk, hk, t);
+  taps[0] = t.x0, taps[1] = t.x1, taps[2] = t.y0, taps[3] = t.y1, taps[4] = t.fx, taps[5] = t.fy;
+  size[0] = wk, size[1] = hk;
+  return CURVIS_OK;
+}
+
+int curvis_sky_mip_mix(uint32_t ck, uint32_t ck1, uint32_t f, uint32_t *out) {
+  if (!out || f > 255u) return CURVIS_E_INVALID;
+  *out = cvk::sky_mip_mix(ck, ck1, f);
+  return CURVIS_OK;
+}
+
+int curvis_sky_mip_pyramid(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t level, uint8_t *out, uint32_t *wl, uint32_t *hl) {
+  if (!rgba || !wl || !hl || w == 0 || h == 0 || level >= cvk::sky_mip_levels(w, h)) return CURVIS_E_INVALID;
+  std::vector<unsigned> cur((size_t)w * h), next;
+  std::memcpy(cur.data(), rgba, cur.size() * 4);
+  unsigned wk = w, hk = h;
+  for (uint32_t k = 0; k < level; ++k) {
+    const unsigned wd = (wk + 1u) >> 1, hd = (hk + 1u) >> 1;
+    next.assign((size_t)wd * hd, 0u);
+    for (unsigned y = 0; y < hd; ++y)
+      for (unsigned x = 0; x < wd; ++x) {
+        const unsigned x0 = 2u * x, x1 = x0 + 1u < wk ? x0 + 1u : wk - 1u, y0 = 2u * y, y1 = y0 + 1u < hk ? y0 + 1u : hk - 1u;
+        next[(size_t)y * wd + x] = cvk::sky_mip_down(cur[(size_t)y0 * wk + x0], cur[(size_t)y0 * wk + x1], cur[(size_t)y1 * wk + x0], cur[(size_t)y1 * wk + x1]);
+      }
+    cur.swap(next);
+    wk = wd, hk = hd;
+  }
+  *wl = wk, *hl = hk;
+  if (out) std::memcpy(out, cur.data(), cur.size() * 4);
+  return CURVIS_OK;
+}
+
+int curvis_ctx_sky_mip_level(curvis_ctx *ctx, int which, uint32_t level, uint8_t *out, uint32_t *w, uint32_t *h) {
+  if (!ctx) return CURVIS_E_INVALID;
+  if (which < 0 || which > 1 || !w || !h) return fail(ctx, CURVIS_E_INVALID, "bad argument");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure_sky_mips(ctx, which)) return rc;
+  const SkyTexture &S = ctx->sky[which];
+  if (level >= S.mip_levels) return fail(ctx, CURVIS_E_INVALID, "sky_mipmap: no such level");
+  const cvk::SkyMipLevel &lv = S.mip_host[level];
+  *w = lv.w, *h = lv.h;
+  if (!out) return CURVIS_OK;
+  HIP_TRY(ctx, hipMemcpyAsync(out, lv.texels, (size_t)lv.w * lv.h * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return CURVIS_OK;
 }
 
 int curvis_render_brute(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *camera,
@@ -957,6 +1041,12 @@ const OptionEntry kOptions[] = {
        c->sky_filter = (int)v;
        return CURVIS_OK;
      }},
+    {"sky_mipmap", OPT_READ(c->sky_mipmap), /* always settable, in either order with "sky_filter": a render call checks the pair */
+     [](curvis_ctx *c, int64_t v) -> int {
+       if (v != 0 && v != 1) return fail(c, CURVIS_E_INVALID, "sky_mipmap must be 0 (off) or 1 (on)");
+       c->sky_mipmap = (int)v;
+       return CURVIS_OK;
+     }},
     {"projection", OPT_READ(c->projection),
      [](curvis_ctx *c, int64_t v) -> int {
        if (v < 0 || v > 2) return fail(c, CURVIS_E_INVALID, "projection must be 0 (perspective), 1 (equirectangular) or 2 (fisheye)");
@@ -975,6 +1065,7 @@ const OptionEntry kOptions[] = {
        c->integrator = (int)v;
        return CURVIS_OK;
      }},
+    OPT_RW(pixel_tiled, int), /* measurement switch: 1 = the efficient renderer enumerates pixels by 8x8 tiles whatever the other options say */
     OPT_RW(device_sampler, int),
     {"device_sampler_min_frames", OPT_READ(c->device_sampler_min_frames),
      [](curvis_ctx *c, int64_t v) -> int {
@@ -998,6 +1089,9 @@ const OptionEntry kOptions[] = {
     OPT_RO("last_relay_parks", c->last_relay_parks),
     OPT_RO("last_relay_waiters", c->last_relay_waiters),
     OPT_RO("last_sampler_path", c->last_sampler_path),
+    OPT_RO("last_pixel_tiled", c->last_pixel_tiled),
+    OPT_RO("last_sky_mip_build_us", c->last_sky_mip_build_us),
+    OPT_RO("last_sky_copy_us", c->last_sky_copy_us),
     OPT_RO("last_sampling_chains", c->last_sampling_chains),
     OPT_RO("last_sampling_prefetched", c->last_sampling_prefetched),
     OPT_RO("prefetches", c->prefetches),
@@ -1149,6 +1243,32 @@ int curvis_selftest_sky_bilinear(curvis_ctx *ctx, uint32_t w, uint32_t h, const 
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipMemcpy(out_taps, dtaps, n * 12 * sizeof(unsigned), hipMemcpyDeviceToHost));
   HIP_TRY(ctx, hipMemcpy(out_rgb, drgb, n * 6, hipMemcpyDeviceToHost));
+  return CURVIS_OK;
+}
+
+int curvis_selftest_sky_mip(curvis_ctx *ctx, uint32_t w, uint32_t h, const uint8_t *rgba, const uint32_t *triples, size_t n, uint8_t *out_rgb) {
+  if (!ctx || !rgba || !triples || !out_rgb || w == 0 || h == 0) return CURVIS_E_INVALID;
+  if (w > kSkyFilterMaxSide || h > kSkyFilterMaxSide) return fail(ctx, CURVIS_E_INVALID, "sky_mipmap: a sky of more than 2^23 texels per side");
+  if (n == 0) return CURVIS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<unsigned> dsky, dchain, din, dout;
+  DeviceBuffer<cvk::SkyMipLevel> dtab;
+  std::vector<cvk::SkyMipLevel> tab;
+  unsigned L = 0;
+  const size_t texels = (size_t)w * h;
+  if (int rc = dsky.reserve(ctx, texels)) return rc;
+  if (int rc = din.reserve(ctx, n * 3)) return rc;
+  if (int rc = dout.reserve(ctx, n)) return rc;
+  HIP_TRY(ctx, hipMemcpy(dsky, rgba, texels * 4, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(din, triples, n * 3 * sizeof(unsigned), hipMemcpyHostToDevice));
+  if (int rc = build_sky_mips(ctx, dsky.p, w, h, dchain, dtab, tab, L)) return rc;
+  hipLaunchKernelGGL(selftest_sky_mip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dtab.p, L, din.p, n, dout.p);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<unsigned> packed(n);
+  HIP_TRY(ctx, hipMemcpy(packed.data(), dout, n * sizeof(unsigned), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i)
+    out_rgb[3 * i] = (uint8_t)(packed[i] & 0xFF), out_rgb[3 * i + 1] = (uint8_t)((packed[i] >> 8) & 0xFF), out_rgb[3 * i + 2] = (uint8_t)((packed[i] >> 16) & 0xFF);
   return CURVIS_OK;
 }
 

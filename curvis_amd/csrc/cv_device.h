@@ -811,6 +811,113 @@ CV_HD unsigned sky_bilinear_blend(unsigned t00, unsigned t01, unsigned t10, unsi
   return 0xFF000000u | ((r + 32768u) >> 16) | (((g + 32768u) >> 16) << 8) | (((b + 32768u) >> 16) << 16);
 }
 
+/* ---- option "sky_mipmap" = 1: the bilinear lookup on a mip pyramid of the sky, the level chosen per ray from how far its neighbours
+ * in the 2 x 2 quad landed (include/curvis_hip.h has the definition: pyramid, footprint, level, colour).  All of it is integer work on
+ * the (Xc, Yc) of the bilinear definition's step 2. */
+struct SkyMipLevel {
+  const unsigned *texels; /* w x h RGBA8; level 0 is the sky itself */
+  unsigned w, h;
+};
+/* sizes: w_{k+1} = (w_k + 1) >> 1, one level per halving until 1 x 1 */
+CV_HD unsigned sky_mip_levels(unsigned w, unsigned h) {
+  unsigned L = 1u;
+  for (unsigned m = w > h ? w : h; m > 1u; m = (m + 1u) >> 1) ++L;
+  return L;
+}
+/* one texel of level k + 1 from the four of level k under it (packed RGBA8): per colour channel (a + b + c + d + 2) >> 2, alpha 255.
+ * Red and blue are summed in one dword, green in another: a channel's sum is at most 1022 and stays inside its 16 bits. */
+CV_HD unsigned sky_mip_down(unsigned a, unsigned b, unsigned c, unsigned d) {
+  const unsigned rb = (a & 0x00FF00FFu) + (b & 0x00FF00FFu) + (c & 0x00FF00FFu) + (d & 0x00FF00FFu) + 0x00020002u;
+  const unsigned g = ((a >> 8) & 0xFFu) + ((b >> 8) & 0xFFu) + ((c >> 8) & 0xFFu) + ((d >> 8) & 0xFFu) + 2u;
+  return 0xFF000000u | ((rb >> 2) & 0x00FF00FFu) | ((g >> 2) << 8);
+}
+/* steps 1 and 2 of the bilinear definition alone: (Xc, Yc), the nearest lookup's raw tx, ty, and -- returned -- whether those lie
+ * outside the sky.  The first lines of sky_bilinear_taps, which keeps its own text. */
+template <bool SHARED = false>
+CV_HD bool sky_fine_indices(const SkyParams &S, double d0, double d1, double d2, unsigned &Xc, unsigned &Yc, unsigned &tx, unsigned &ty,
+                            double y_pi = 0.0, double y_two_pi = 0.0) {
+  const unsigned fine_w = S.w << 8, fine_h = S.h << 8;
+  SkyParams F = S;
+  F.w = fine_w;
+  F.h = fine_h;
+  unsigned X, Y;
+  sky_indices<SHARED>(F, d0, d1, d2, X, Y, y_pi, y_two_pi);
+  tx = X >> 8;
+  ty = Y >> 8;
+  Xc = X < fine_w - 1u ? X : fine_w - 1u;
+  Yc = Y < fine_h - 1u ? Y : fine_h - 1u;
+  return tx >= S.w || ty >= S.h;
+}
+/* footprint: the largest of |wrap(Xc' - Xc)| and |Yc' - Yc| over the horizontal partner (Xh, Yh) and the vertical one (Xv, Yv) of the
+ * ray's quad; a partner with !ok (outside the frame, capped, on the other sky) contributes nothing.  fine_w = 256 w <= 2^31; wrap
+ * reduces modulo fine_w into [-fine_w / 2, fine_w / 2). */
+CV_HD unsigned sky_mip_wrap_abs(unsigned Xc, unsigned Xp, unsigned fine_w) {
+  const unsigned d = Xp >= Xc ? Xp - Xc : Xp + (fine_w - Xc); /* (Xp - Xc) mod fine_w */
+  return d < (fine_w >> 1) ? d : fine_w - d;
+}
+CV_HD unsigned sky_mip_rho(unsigned Xc, unsigned Yc, unsigned fine_w, unsigned Xh, unsigned Yh, bool okh, unsigned Xv, unsigned Yv, bool okv) {
+  unsigned rho = 0u;
+  if (okh) {
+    const unsigned dx = sky_mip_wrap_abs(Xc, Xh, fine_w), dy = Yh >= Yc ? Yh - Yc : Yc - Yh;
+    rho = dx > dy ? dx : dy;
+  }
+  if (okv) {
+    const unsigned dx = sky_mip_wrap_abs(Xc, Xv, fine_w), dy = Yv >= Yc ? Yv - Yc : Yc - Yv;
+    const unsigned m = dx > dy ? dx : dy;
+    rho = rho > m ? rho : m;
+  }
+  return rho;
+}
+/* level k and the weight f (in 1/256) of level k + 1, for a pyramid of L >= 1 levels: total for every 32-bit rho */
+CV_HD void sky_mip_level(unsigned rho, unsigned L, unsigned &k, unsigned &f) {
+  k = 0u;
+  f = 0u;
+  if (rho >= 256u) {
+    k = 23u - (unsigned)__builtin_clz(rho); /* msb(rho) - 8 */
+    f = (rho >> k) & 255u;
+  }
+  if (k >= L - 1u) {
+    k = L - 1u;
+    f = 0u;
+  }
+}
+/* steps 3 and 4 of the bilinear definition on level k: (Xk, Yk) = (Xc >> k, Yc >> k) over wk x hk texels; Xk < 256 wk always holds.
+ * Fills the columns, rows and weights of t; tx, ty and oob are the nearest lookup's and are not touched. */
+CV_HD void sky_mip_taps(unsigned Xk, unsigned Yk, unsigned wk, unsigned hk, SkyTaps &t) {
+  const unsigned U = Xk >= 128u ? Xk - 128u : Xk + (wk << 8) - 128u;
+  t.x0 = U >> 8;
+  t.fx = U & 255u;
+  t.x1 = t.x0 + 1u == wk ? 0u : t.x0 + 1u;
+  const unsigned V = Yk >= 128u ? Yk - 128u : 0u;
+  t.y0 = V >> 8;
+  t.fy = V & 255u;
+  t.y1 = t.y0 + 1u < hk ? t.y0 + 1u : hk - 1u;
+}
+/* the blend of the colours of level k and level k + 1: per channel ((256 - f) ck + f ck1 + 128) >> 8, alpha 255 */
+CV_HD unsigned sky_mip_mix(unsigned ck, unsigned ck1, unsigned f) {
+  const unsigned g = 256u - f;
+  const unsigned r = (g * (ck & 255u) + f * (ck1 & 255u) + 128u) >> 8;
+  const unsigned gr = (g * ((ck >> 8) & 255u) + f * ((ck1 >> 8) & 255u) + 128u) >> 8;
+  const unsigned b = (g * ((ck >> 16) & 255u) + f * ((ck1 >> 16) & 255u) + 128u) >> 8;
+  return 0xFF000000u | r | (gr << 8) | (b << 16);
+}
+/* the whole per-ray colour from (Xc, Yc, rho) over the level table of a sky: the gathers of both levels are independent and are
+ * issued together, four when f = 0 */
+CV_HD unsigned sky_mip_colour(const SkyMipLevel *tab, unsigned L, unsigned Xc, unsigned Yc, unsigned rho) {
+  unsigned k, f;
+  sky_mip_level(rho, L, k, f);
+  const SkyMipLevel A = tab[k], B = tab[f ? k + 1u : k];
+  SkyTaps a, b;
+  sky_mip_taps(Xc >> k, Yc >> k, A.w, A.h, a);
+  const unsigned *a0 = A.texels + (size_t)a.y0 * A.w, *a1 = A.texels + (size_t)a.y1 * A.w;
+  const unsigned a00 = a0[a.x0], a01 = a0[a.x1], a10 = a1[a.x0], a11 = a1[a.x1];
+  if (f == 0u) return sky_bilinear_blend(a00, a01, a10, a11, a.fx, a.fy);
+  sky_mip_taps(Xc >> (k + 1u), Yc >> (k + 1u), B.w, B.h, b);
+  const unsigned *b0 = B.texels + (size_t)b.y0 * B.w, *b1 = B.texels + (size_t)b.y1 * B.w;
+  const unsigned b00 = b0[b.x0], b01 = b0[b.x1], b10 = b1[b.x0], b11 = b1[b.x1];
+  return sky_mip_mix(sky_bilinear_blend(a00, a01, a10, a11, a.fx, a.fy), sky_bilinear_blend(b00, b01, b10, b11, b.fx, b.fy), f);
+}
+
 }  // namespace cvk
 
 #endif /* CURVIS_CV_DEVICE_H */

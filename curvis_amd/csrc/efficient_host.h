@@ -155,16 +155,25 @@ int make_pixel_params(curvis_ctx *ctx, uint32_t n_frames, uint32_t W, uint32_t H
   return ensure_pixel_recips(ctx, (double)W, (double)H, Q.recips);
 }
 
-/* K3 over n_frames frames of Q.W x Q.H pixels: linear pixel order, or -- supersampled -- 8x8 tiles of the fine grid, four per workgroup */
+/* K3 over n_frames frames of Q.W x Q.H pixels: linear pixel order, or -- supersampled, or with option "sky_mipmap" (filter = 2), whose
+ * quads need a lane's vertical neighbour in its wave -- 8x8 tiles of the fine grid, four per workgroup */
 int launch_pixel_kernel(curvis_ctx *ctx, EfficientPixelParams Q, uint32_t n_frames, uint32_t ss, uint32_t filter, uint32_t projection) {
   Q.projection = (int)projection;
+  const bool tiled = ss > 1u || filter == 2u || ctx->pixel_tiled != 0; /* "pixel_tiled": the enumeration alone, for measurements */
   const unsigned long long tiles = (unsigned long long)((Q.W + 7u) / 8u) * ((Q.H + 7u) / 8u);
-  if (ss > 1u && (tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
-  const unsigned long long groups = ss > 1u ? (tiles + 3ull) / 4ull : ((unsigned long long)Q.W * Q.H + 255ull) / 256ull;
+  if (tiled && (tiles + 3ull) / 4ull > 0x7FFFFFFFull) return fail(ctx, CURVIS_E_INVALID, "frame or batch too large");
+  const unsigned long long groups = tiled ? (tiles + 3ull) / 4ull : ((unsigned long long)Q.W * Q.H + 255ull) / 256ull;
+  ctx->last_pixel_tiled = tiled ? 1 : 0;
   with_launch_shape(0, false, ss, filter, projection, false, [&](auto S) { /* the metric kind and the step flavour mean nothing to K3 */
     using T = decltype(S);
     const dim3 grid((unsigned)groups, n_frames);
-    if constexpr (T::SS > 1) hipLaunchKernelGGL((efficient_pixel_ss_kernel<T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, Q);
+    if constexpr (T::FILTER == 2) {
+      WithSkyMip<EfficientPixelParams> QM;
+      static_cast<EfficientPixelParams &>(QM) = Q;
+      QM.mip = sky_mip_args(ctx);
+      hipLaunchKernelGGL((efficient_pixel_ss_kernel<T::SS, 2, T::PROJ>), grid, dim3(256), 0, ctx->stream, QM);
+    } else if constexpr (T::SS > 1) hipLaunchKernelGGL((efficient_pixel_ss_kernel<T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, Q);
+    else if (tiled) hipLaunchKernelGGL((efficient_pixel_ss_kernel<1, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, Q);
     else hipLaunchKernelGGL((efficient_pixel_kernel<T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, Q);
   });
   HIP_TRY(ctx, hipGetLastError());
@@ -913,6 +922,9 @@ int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *r
   }
   if (!ctx->sky[0].texels || !ctx->sky[1].texels) return fail(ctx, CURVIS_E_NO_SKY, "both background images must be set");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (c.filter == 2u) /* option "sky_mipmap": the skies' mip chains, built on first use, before anything of the call is timed */
+    for (int k = 0; k < 2; ++k)
+      if ((rc = ensure_sky_mips(ctx, k))) return rc;
   const cvk::MetricParams MP = make_metric(*metric);
 
   /* step 1 (host): camera direction on the background space and the tangent->background rotation */
@@ -983,6 +995,9 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   if (!cvk::efficient_frame_pose(cam->pos[2], cam->pos[3], P.frame)) /* src/systems.rs:393-397, :411 */
     return fail(ctx, CURVIS_E_PARALLEL, "v1 and v2 must not be parallel (src/algebra.rs:95-97, camera on the x axis)");
   for (int k = 0; k < 2; ++k) P.sky[k] = make_sky_params(ctx, k);
+  if (filter == 2u) /* option "sky_mipmap": the skies' mip chains, built on first use */
+    for (int k = 0; k < 2; ++k)
+      if ((rc = ensure_sky_mips(ctx, k))) return rc;
   P.W = W;
   P.H = H;
   P.tiles_x = (W + 7) / 8;
@@ -1007,7 +1022,13 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, shape.projection, shape.adapt, [&](auto S) {
     using T = decltype(S);
     const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
-    if constexpr (T::ADAPT != 0) hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, P);
+    if constexpr (T::FILTER == 2) {
+      using Base = std::conditional_t<T::ADAPT != 0, DirectParamsAdapt, DirectParams>;
+      WithSkyMip<Base> PM;
+      static_cast<Base &>(PM) = P;
+      PM.mip = sky_mip_args(ctx);
+      hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, 2, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, PM);
+    } else if constexpr (T::ADAPT != 0) hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, P);
     else hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, static_cast<const DirectParams &>(P));
   });
   HIP_TRY(ctx, hipGetLastError());

@@ -86,6 +86,19 @@ struct SkyTexture {
   void *texels = nullptr;
   bool owned = false;
   unsigned w = 0, h = 0;
+  /* option "sky_mipmap": levels 1 .. mip_levels - 1 of the mip chain in one allocation, and the level table the kernels index
+   * (entry 0 points at `texels`); built by the first render call with the option on (render_host.h ensure_sky_mips), dropped with the
+   * texels.  mip_levels = 0: not built -- nothing is allocated for a context that never sets the option */
+  DeviceBuffer<unsigned> mip_texels;
+  DeviceBuffer<cvk::SkyMipLevel> mip_table;
+  std::vector<cvk::SkyMipLevel> mip_host; /* the table's host copy */
+  unsigned mip_levels = 0;
+  void drop_mips() {
+    mip_texels = DeviceBuffer<unsigned>();
+    mip_table = DeviceBuffer<cvk::SkyMipLevel>();
+    mip_host.clear();
+    mip_levels = 0;
+  }
   SkyTexture() = default;
   SkyTexture(const SkyTexture &) = delete;
   SkyTexture &operator=(const SkyTexture &) = delete;
@@ -95,6 +108,7 @@ struct SkyTexture {
   size_t bytes() const { return (size_t)w * h * 4; }
   /* drop the texels (free them if they are ours) and take a new shape; nothing is allocated yet */
   int reset(curvis_ctx *ctx, unsigned w_, unsigned h_) {
+    drop_mips(); /* first: a failed hipFree below must not leave a chain of the old texels attached */
     if (texels && owned) HIP_TRY(ctx, hipFree(texels));
     texels = nullptr;
     owned = false;

@@ -18,12 +18,14 @@ struct Args {
   std::string gpu_png = "auto"; /* video: PNG front end on the device (curvis_ctx_deflate_frames): auto = with the fast writer, on, off */
   int supersample = 1; /* rays per pixel and axis, averaged on the device (library option "supersample"): 1, 2, 4 or 8 */
   int sky_filter = 0; /* sky lookup (library option "sky_filter"): 0 nearest texel, 1 bilinear */
+  int sky_mipmap = 0; /* --sky-mipmap on|off (library option "sky_mipmap"): the bilinear lookup on a mip pyramid of the sky, on top of --sky-filter bilinear */
   int projection = 0; /* pixel -> direction (library option "projection"): 0 perspective, 1 equirectangular, 2 fisheye */
   long long step_scale = 0; /* --step-scale L0 as library option "step_scale" = 256 L0: 0 off, else the Euler step grows as |l| / L0 outside L0 */
   int integrator = 0; /* --integrator euler|heun (library option "integrator"): 0 forward Euler, 1 Heun's method, two Euler steps averaged */
 };
 int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
 int g_sky_filter = 0;  /* Args::sky_filter, likewise */
+int g_sky_mipmap = 0;  /* Args::sky_mipmap, likewise */
 int g_projection = 0;  /* Args::projection, likewise */
 long long g_step_scale = 0; /* Args::step_scale, likewise */
 int g_integrator = 0;  /* Args::integrator, likewise */
@@ -42,7 +44,7 @@ void usage() {
       "              [--sky-broadcast rccl|upload] [--writers T] [--resume] [--png-level -1..9] [--gpu-png auto|on|off]\n"
       "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n"
       "              [--projection perspective|equirectangular|fisheye] [--step-scale L0]\n"
-      "              [--integrator euler|heun]\n");
+      "              [--integrator euler|heun] [--sky-mipmap on|off]\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -95,6 +97,11 @@ Args parse_args(int argc, char **argv) {
       take(val);
       if (val != "nearest" && val != "bilinear") die("error: --sky-filter must be nearest or bilinear", 2);
       a.sky_filter = g_sky_filter = val == "bilinear" ? 1 : 0;
+    }
+    else if (key == "--sky-mipmap") {
+      take(val);
+      if (val != "on" && val != "off") die("error: --sky-mipmap must be on or off", 2);
+      a.sky_mipmap = g_sky_mipmap = val == "on" ? 1 : 0;
     }
     else if (key == "--projection") {
       take(val);
@@ -267,6 +274,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
   }
   if (g_supersample != 1) check(curvis_ctx_set_option(ctx, "supersample", g_supersample), ctx, what);
   if (g_sky_filter != 0) check(curvis_ctx_set_option(ctx, "sky_filter", g_sky_filter), ctx, what);
+  if (g_sky_mipmap != 0) check(curvis_ctx_set_option(ctx, "sky_mipmap", g_sky_mipmap), ctx, what);
   if (g_projection != 0) check(curvis_ctx_set_option(ctx, "projection", g_projection), ctx, what);
   if (g_step_scale != 0) check(curvis_ctx_set_option(ctx, "step_scale", g_step_scale), ctx, what);
   if (g_integrator != 0) check(curvis_ctx_set_option(ctx, "integrator", g_integrator), ctx, what);

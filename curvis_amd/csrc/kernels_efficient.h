@@ -401,8 +401,9 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
  * (106 SGPRs instead of 76, seven waves per SIMD instead of eight); the lookup as shade_ray's sky_lookup and the statistics as a
  * function each change the instructions of all eight instantiations (register allocation, waits; 20 to 120 lines each), which
  * would need a timing against the parent that has not been made. */
-template <int SS, int FILTER = 0, int PROJ = 0>
-__global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const EfficientPixelParams P) {
+template <int SS, int FILTER = 0, int PROJ = 0> /* FILTER = 2 (option "sky_mipmap"): also with SS = 1 -- a lane of the linear kernel has no vertical
+  neighbour in its wave, so the mip-mapped lookup of an unsupersampled call takes this enumeration with a plain store per lane */
+__global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const std::conditional_t<FILTER == 2, WithSkyMip<EfficientPixelParams>, EfficientPixelParams> P) {
   __shared__ unsigned s_cnt[5];
   const unsigned f = blockIdx.y;
   const unsigned tiles_x = (P.W + 7u) >> 3;
@@ -414,6 +415,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const Efficient
   if (threadIdx.x < 5u) s_cnt[threadIdx.x] = 0u;
   bool pos = false, neg = false, none = false, oob = false;
   unsigned texel = 0xFF000000u;
+  [[maybe_unused]] unsigned Xc = 0u, Yc = 0u; /* FILTER = 2: the lane's indices on its sky, for the exchange behind the branch */
   if (valid) {
     const unsigned off = P.tab_off[f], n = P.tab_n[f];
     double fin[3], space;
@@ -427,7 +429,9 @@ __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const Efficient
       if (k == 0 ? pos : neg) {
         const cvk::SkyParams &S = P.sky[k];
         unsigned tx, ty;
-        if constexpr (FILTER != 0) { /* the sky's size, pointer and rotation stay scalar operands: the taps' integer work is per lane */
+        if constexpr (FILTER == 2) {
+          if (cvk::sky_fine_indices<true>(S, fin[0], fin[1], fin[2], Xc, Yc, tx, ty, P.recips.y_pi, P.recips.y_two_pi)) oob = true;
+        } else if constexpr (FILTER != 0) { /* the sky's size, pointer and rotation stay scalar operands: the taps' integer work is per lane */
           if (sky_lookup_bilinear<true>(S, fin[0], fin[1], fin[2], tx, ty, texel, P.recips.y_pi, P.recips.y_two_pi)) oob = true;
         } else {
           cvk::sky_indices<true>(S, fin[0], fin[1], fin[2], tx, ty, P.recips.y_pi, P.recips.y_two_pi);
@@ -439,7 +443,9 @@ __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const Efficient
       }
     }
   }
-  resolve_store<SS>(P.fb, P.W, P.H, f, px, py, valid, texel);
+  if constexpr (FILTER == 2) texel = sky_mip_shade(P.mip, P.sky, pos ? 1u : neg ? 2u : 0u, Xc, Yc); /* the whole wave */
+  if constexpr (SS > 1) resolve_store<SS>(P.fb, P.W, P.H, f, px, py, valid, texel);
+  else if (valid) store_rgb8(P.fb + ((size_t)f * P.W * P.H + (size_t)py * P.W + px) * 3u, texel);
   const unsigned long long vm = __builtin_amdgcn_ballot_w64(valid);
   const unsigned n_pos = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(pos)), n_neg = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(neg));
   const unsigned n_none = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(none)), n_oob = (unsigned)__popcll(__builtin_amdgcn_ballot_w64(oob));
@@ -488,9 +494,11 @@ struct DirectParamsAdapt : DirectParams { /* the ADAPT instantiations' argument:
 /* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
 template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter", PROJ: option "projection", ADAPT: options "step_scale" (1) and "integrator" (2) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 4 : 6)))
-void direct_kernel(const std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams> P) {
+void direct_kernel(const std::conditional_t<FILTER == 2, WithSkyMip<std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>>,
+                                            std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>> P) {
   [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */
   if constexpr (SS > 1) texel_ss = 0xFF000000u;
+  [[maybe_unused]] unsigned which = 0u, Xc = 0u, Yc = 0u; /* FILTER = 2 (option "sky_mipmap"): the lane's sky (0: none) and its indices on it */
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -531,7 +539,10 @@ void direct_kernel(const std::conditional_t<ADAPT != 0, DirectParamsAdapt, Direc
       unsigned tx, ty;
       /* shade_ray's sky_lookup (kernels_epilogue.h) written out: called from here it reorders the values live across the Euler loop
        * above, and the registers of its floating-point instructions change with them (up to 450 changed lines per instantiation) */
-      if constexpr (FILTER != 0) {
+      if constexpr (FILTER == 2) { /* the colour follows behind the branch, from the whole wave (sky_mip_shade) */
+        if (cvk::sky_fine_indices(S, fin[0], fin[1], fin[2], Xc, Yc, tx, ty)) oob = 1;
+        which = code == cvk::CODE_POS ? 1u : 2u;
+      } else if constexpr (FILTER != 0) {
         if (sky_lookup_bilinear<false>(S, fin[0], fin[1], fin[2], tx, ty, texel)) oob = 1;
       } else {
         cvk::sky_indices(S, fin[0], fin[1], fin[2], tx, ty);
@@ -545,14 +556,22 @@ void direct_kernel(const std::conditional_t<ADAPT != 0, DirectParamsAdapt, Direc
     } else {
       none = 1;
     }
-    if constexpr (SS == 1) {
+    if constexpr (FILTER == 2) {
+    } else if constexpr (SS == 1) {
       unsigned char *dst = P.fb + ((size_t)py * P.W + px) * 3;
       store_rgb8(dst, texel);
     } else {
       texel_ss = texel;
     }
   }
-  if constexpr (SS > 1) resolve_store<SS>(P.fb, P.W, P.H, 0u, px, py, valid, texel_ss);
+  if constexpr (FILTER == 2) {
+    const unsigned texel = sky_mip_shade(P.mip, P.sky, which, Xc, Yc);
+    if constexpr (SS == 1) {
+      if (valid) store_rgb8(P.fb + ((size_t)py * P.W + px) * 3, texel);
+    } else {
+      resolve_store<SS>(P.fb, P.W, P.H, 0u, px, py, valid, texel);
+    }
+  } else if constexpr (SS > 1) resolve_store<SS>(P.fb, P.W, P.H, 0u, px, py, valid, texel_ss);
   flush_frame_counts(P.counters, 0u, valid, steps, 1u, pos, neg, none, oob);
 }
 

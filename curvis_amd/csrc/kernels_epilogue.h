@@ -162,4 +162,58 @@ __device__ __forceinline__ void resolve_store(unsigned char *fb, unsigned W, uns
   }
 }
 
+/* ---- option "sky_mipmap" = 1 (the kernels' FILTER = 2): the level tables of the two skies (device memory, levels[k] entries each).
+ * They travel in a struct DERIVED from the kernel's argument struct, behind its last member, so that no argument of any other
+ * instantiation moves. */
+struct SkyMipArgs {
+  const cvk::SkyMipLevel *tab[2];
+  unsigned levels[2];
+};
+template <typename Base>
+struct WithSkyMip : Base {
+  SkyMipArgs mip;
+};
+/* Called by EVERY lane of a wave that holds one 8x8 tile of rays whose origin is even in both absolute ray coordinates: `which` is 0
+ * (no sky: capped, or outside the frame), 1 (+l sky) or 2 (-l sky), (Xc, Yc) the lane's indices on its own sky.  The lanes exchange the
+ * three with the horizontal (lane ^ 1) and vertical (lane ^ 8) partner of their 2 x 2 quad on DPP, form the footprint, the level and
+ * its fraction (cv_device.h sky_mip_rho / sky_mip_level) and return the colour; black for which = 0. */
+__device__ __forceinline__ unsigned sky_mip_shade(const SkyMipArgs &A, const cvk::SkyParams *sky, unsigned which, unsigned Xc, unsigned Yc) {
+  const unsigned Xh = lane_xor<1>(Xc), Yh = lane_xor<1>(Yc), wh = lane_xor<1>(which);
+  const unsigned Xv = lane_xor<8>(Xc), Yv = lane_xor<8>(Yc), wv = lane_xor<8>(which);
+  unsigned texel = 0xFF000000u;
+  if (which != 0u) {
+    const bool second = which == 2u;
+    const unsigned fine_w = (second ? sky[1].w : sky[0].w) << 8;
+    const unsigned rho = cvk::sky_mip_rho(Xc, Yc, fine_w, Xh, Yh, wh == which, Xv, Yv, wv == which);
+    texel = cvk::sky_mip_colour(second ? A.tab[1] : A.tab[0], second ? A.levels[1] : A.levels[0], Xc, Yc, rho);
+  }
+  return texel;
+}
+
+/* level k + 1 of a sky's mip chain from level k (cv_device.h sky_mip_down): one thread per output texel, a row of the grid per output
+ * row; a thread reads the 2 x 2 texels under its own -- two neighbouring dwords of two rows, so a wave reads two whole runs of 512
+ * bytes -- with the last column and row repeated where the source size is odd.  Bandwidth-bound: 5/4 of the source level's bytes. */
+__global__ __launch_bounds__(256) void sky_mip_kernel(const unsigned *src, unsigned ws, unsigned hs, unsigned *dst, unsigned wd, unsigned hd) {
+  const unsigned x = blockIdx.x * 256u + threadIdx.x;
+  for (unsigned y = blockIdx.y; y < hd; y += gridDim.y) {
+    if (x < wd) {
+      const unsigned x0 = 2u * x, x1 = x0 + 1u < ws ? x0 + 1u : ws - 1u;
+      const unsigned y0 = 2u * y, y1 = y0 + 1u < hs ? y0 + 1u : hs - 1u;
+      const unsigned *r0 = src + (size_t)y0 * ws, *r1 = src + (size_t)y1 * ws;
+      dst[(size_t)y * wd + x] = cvk::sky_mip_down(r0[x0], r0[x1], r1[x0], r1[x1]);
+    }
+  }
+}
+
+/* the per-ray function of option "sky_mipmap" on chosen (Xc, Yc, rho) triples over one sky's level table (tests) */
+__global__ void selftest_sky_mip_kernel(const cvk::SkyMipLevel *tab, unsigned L, const unsigned *triples, size_t n, unsigned *out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned fine_w = tab[0].w << 8, fine_h = tab[0].h << 8;
+  unsigned Xc = triples[3 * i], Yc = triples[3 * i + 1];
+  if (Xc >= fine_w) Xc = fine_w - 1u; /* the definition's Xc, Yc lie inside the virtual sky: the gathers below must, too */
+  if (Yc >= fine_h) Yc = fine_h - 1u;
+  out[i] = cvk::sky_mip_colour(tab, L, Xc, Yc, triples[3 * i + 2]);
+}
+
 }  // namespace

@@ -46,6 +46,9 @@ struct IntegrateParamsAdapt : IntegrateParams {
 };
 template <int ADAPT>
 using IntegrateArgs = std::conditional_t<ADAPT != 0, IntegrateParamsAdapt, IntegrateParams>;
+/* FILTER = 2 (option "sky_mipmap"): either of the two with the skies' level tables appended (kernels_epilogue.h WithSkyMip) */
+template <int ADAPT, int FILTER>
+using IntegrateArgsF = std::conditional_t<FILTER == 2, WithSkyMip<IntegrateArgs<ADAPT>>, IntegrateArgs<ADAPT>>;
 
 struct ShadeParams {
   cvk::MetricParams metric;
@@ -247,13 +250,15 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
  * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame.
  * SS: supersampling factor (1: one ray per output pixel; 2, 4, 8: P is in units of the fine grid and the epilogue averages,
  * kernels_epilogue.h resolve_store; FUSED only). */
-template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter" (FUSED only);
+template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter" (FUSED only),
+  2 with option "sky_mipmap" on top: the epilogue finds every ray's (Xc, Yc), the wave exchanges them inside its 2 x 2 quads and each lane
+  blends two levels of the sky's mip chain (kernels_epilogue.h sky_mip_shade);
   PROJ: 0 the reference's perspective mapping, 1 option "projection" != 0 (P.projection says which; FUSED only);
   ADAPT: 1 option "step_scale" != 0: every step takes cv_device.h step_delta(P.delta, P.kappa, l) instead of P.delta (the fused kernels and
   the debug dump's staged PHI kernel, fast step only); 2 option "integrator" = 1: a step is cv_device.h ray_step_heun with that delta_k
   (kappa = +0 while "step_scale" is off: step_delta then returns P.delta for every l) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7) - (ADAPT == 2 ? 1 : 0))))
-void geodesic_static(const IntegrateArgs<ADAPT> P) { /* the Heun step holds the saved state across two stages, four register pairs more:
+void geodesic_static(const IntegrateArgsF<ADAPT, FILTER> P) { /* the Heun step holds the saved state across two stages, four register pairs more:
   at 7 (5) waves the loop would spill them, so the ADAPT = 2 kernels ask for one wave less */
   static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");
   static_assert(FILTER == 0 || (FUSED && !PHI), "the filtered lookup exists in the fused epilogues only");
@@ -324,7 +329,24 @@ void geodesic_static(const IntegrateArgs<ADAPT> P) { /* the Heun step holds the 
   valid = id2 < P.total_rays && decode_ray(P, id2, frame, px, py);
   const size_t slot = valid ? (size_t)frame * P.W * P.H + (size_t)py * P.W + px : 0;
   [[maybe_unused]] unsigned seen = 0u; /* SS > 1: what the lane's ray saw, for the resolve behind the branch */
-  if (valid) {
+  if constexpr (FILTER == 2) {
+    unsigned which = 0u, Xc = 0u, Yc = 0u; /* the lane's sky (0: none) and its indices on it, for the exchange */
+    if (valid) {
+      if (code != cvk::CODE_NONE) {
+        double d0, d1, d2;
+        cvk::ray_direction<KIND>(M, q, d0, d1, d2);
+        unsigned tx, ty;
+        if (cvk::sky_fine_indices(P.sky[code == cvk::CODE_POS ? 0 : 1], d0, d1, d2, Xc, Yc, tx, ty)) oob = 1;
+        which = code == cvk::CODE_POS ? 1u : 2u;
+      }
+      pos = (code == cvk::CODE_POS);
+      neg = (code == cvk::CODE_NEG);
+      none = (code == cvk::CODE_NONE);
+    }
+    seen = sky_mip_shade(P.mip, P.sky, which, Xc, Yc); /* the whole wave: lanes outside the frame answer "none" */
+    if constexpr (SS == 1)
+      if (valid) store_rgb8(P.fb + slot * 3, seen);
+  } else if (valid) {
     if (FUSED) {
       unsigned tx, ty;
       const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);

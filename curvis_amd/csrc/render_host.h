@@ -104,6 +104,13 @@ struct curvis_ctx {
                                kernels' epilogues average them (kernels_epilogue.h resolve_store); frames stay res_x x res_y */
   int sky_filter = 0;       /* 0: a ray takes the nearest sky texel (the reference); 1: the bilinear blend of the four around its
                                direction, defined in include/curvis_hip.h (cv_device.h sky_bilinear_taps / sky_bilinear_blend) */
+  int sky_mipmap = 0;       /* 1 (on top of sky_filter = 1): the bilinear blend on a mip pyramid of the sky, the level chosen per ray from
+                               its quad neighbours -- defined in include/curvis_hip.h (cv_device.h sky_mip_*; the kernels' FILTER = 2) */
+  int pixel_tiled = 0;      /* measurement switch (tools/gpu_sky_mipmap_cost.py): 1 = the efficient renderer's per-pixel launch enumerates
+                               pixels by 8x8 tiles even where the linear kernel would do, so that the enumeration is timed on its own */
+  int64_t last_sky_mip_build_us = 0; /* HIP-event time of the last mip chain build (its launches alone), microseconds */
+  int64_t last_sky_copy_us = 0;      /* HIP-event time of the last device-to-device sky copy (curvis_ctx_set_sky_device, copy = 1) */
+  int last_pixel_tiled = 0; /* the efficient renderer's last per-pixel launch: 0 efficient_pixel_kernel (linear), 1 the tile-enumerating one */
   int projection = 0;       /* 0: the reference's perspective camera; 1: equirectangular; 2: equidistant fisheye -- pixel -> camera-space
                                vector, defined in include/curvis_hip.h (cv_device.h camera_pixel_vector) */
   int integrator = 0;       /* 0: forward Euler, the reference's loop; 1: Heun's method composed of two Euler steps -- defined in
@@ -195,7 +202,7 @@ auto with_flag(bool flag, F &&f) {
 /* The whole shape of a render launch -- metric kind, step flavour, supersampling factor, sky filter, projection -- as ONE type:
  * with_launch_shape(kind, fast, ss, filter, projection, [&](auto S) { using T = decltype(S); ... T::KIND, T::FAST, T::SS, T::FILTER,
  * T::PROJ ... }) calls the lambda once.  ss is 1, 2, 4 or 8 and filter 0 or 1: the writers of the options "supersample" and
- * "sky_filter" admit nothing else.  PROJ is 1 for every projection but the perspective one: which of them is a kernel argument. */
+ * "sky_filter" admit nothing else; filter = 2 is "sky_filter" = 1 with "sky_mipmap" = 1 on top (prepare_call_shape).  PROJ is 1 for every projection but the perspective one: which of them is a kernel argument. */
 template <int KIND_, bool FAST_, int SS_, int FILTER_, int PROJ_, int ADAPT_ = 0>
 struct LaunchShape {
   static constexpr int KIND = KIND_, SS = SS_, FILTER = FILTER_, PROJ = PROJ_, ADAPT = ADAPT_;
@@ -214,11 +221,13 @@ auto with_launch_shape(int kind, bool fast, uint32_t ss, uint32_t filter, uint32
           if (adapt) {
             auto with_adapt = [&](auto D) {
               constexpr int ADAPT = decltype(D)::value;
+              if (filter == 2u) return projection ? f(LaunchShape<KIND, FAST, SS, 2, 1, ADAPT>{}) : f(LaunchShape<KIND, FAST, SS, 2, 0, ADAPT>{});
               if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1, ADAPT>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1, ADAPT>{});
               return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0, ADAPT>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0, ADAPT>{});
             };
             return adapt == 2 ? with_adapt(std::integral_constant<int, 2>{}) : with_adapt(std::integral_constant<int, 1>{});
           }
+        if (filter == 2u) return projection ? f(LaunchShape<KIND, FAST, SS, 2, 1>{}) : f(LaunchShape<KIND, FAST, SS, 2, 0>{});
         if (projection) return filter ? f(LaunchShape<KIND, FAST, SS, 1, 1>{}) : f(LaunchShape<KIND, FAST, SS, 0, 1>{});
         return filter ? f(LaunchShape<KIND, FAST, SS, 1, 0>{}) : f(LaunchShape<KIND, FAST, SS, 0, 0>{});
       };
@@ -271,6 +280,10 @@ int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_f
   if (int rc = step_scale_kappa(ctx, delta, s.kappa, s.adapt)) return rc;
   s.ss = (uint32_t)ctx->supersample;
   s.filter = (uint32_t)ctx->sky_filter;
+  if (ctx->sky_mipmap) { /* the kernels' FILTER = 2: the mip-mapped lookup acts on top of the bilinear one */
+    if (!s.filter) return fail(ctx, CURVIS_E_INVALID, "sky_mipmap = 1: the mip-mapped lookup acts on top of the bilinear filter (set sky_filter = 1)");
+    s.filter = 2u;
+  }
   if (s.filter)
     for (const auto &sky : ctx->sky)
       if (sky.texels && (sky.w > kSkyFilterMaxSide || sky.h > kSkyFilterMaxSide))
@@ -444,6 +457,62 @@ cvk::SkyParams make_sky_params(const curvis_ctx *ctx, int k) {
   return S;
 }
 
+/* ---- option "sky_mipmap": the mip chain of a sky.  Level k + 1 has (w_k + 1) >> 1 x (h_k + 1) >> 1 texels, down to 1 x 1; levels >= 1
+ * share one allocation (a third of the sky), level 0 is the sky's own texels -- the caller's buffer for a borrowed sky.  One launch of
+ * sky_mip_kernel per level on the context's stream; the table of {pointer, w, h} per level is what the FILTER = 2 kernels index. */
+int build_sky_mips(curvis_ctx *ctx, const unsigned *level0, unsigned w, unsigned h, DeviceBuffer<unsigned> &texels,
+                   DeviceBuffer<cvk::SkyMipLevel> &table, std::vector<cvk::SkyMipLevel> &host, unsigned &levels) {
+  const unsigned L = cvk::sky_mip_levels(w, h);
+  size_t total = 0;
+  {
+    unsigned wk = w, hk = h;
+    for (unsigned k = 1; k < L; ++k) {
+      wk = (wk + 1u) >> 1, hk = (hk + 1u) >> 1;
+      total += (size_t)wk * hk;
+    }
+  }
+  if (int rc = texels.reserve(ctx, total ? total : 1)) return rc;
+  if (int rc = table.reserve(ctx, L)) return rc;
+  host.assign(L, cvk::SkyMipLevel{level0, w, h});
+  if (int rc = ctx->ev0.ensure(ctx)) return rc;
+  if (int rc = ctx->ev1.ensure(ctx)) return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream)); /* the launches alone, by HIP events: option "last_sky_mip_build_us" */
+  size_t off = 0;
+  for (unsigned k = 1; k < L; ++k) {
+    const cvk::SkyMipLevel &s = host[k - 1];
+    cvk::SkyMipLevel &d = host[k];
+    d.w = (s.w + 1u) >> 1, d.h = (s.h + 1u) >> 1;
+    d.texels = texels.p + off;
+    off += (size_t)d.w * d.h;
+    const dim3 grid((d.w + 255u) / 256u, d.h < 65535u ? d.h : 65535u);
+    hipLaunchKernelGGL(sky_mip_kernel, grid, dim3(256), 0, ctx->stream, s.texels, s.w, s.h, const_cast<unsigned *>(d.texels), d.w, d.h);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(table, host.data(), sizeof(cvk::SkyMipLevel) * L, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); /* `host` is pageable memory: the copy has left it */
+  float build_ms = 0.f;
+  HIP_TRY(ctx, hipEventElapsedTime(&build_ms, ctx->ev0, ctx->ev1));
+  ctx->last_sky_mip_build_us = (int64_t)(build_ms * 1000.0f + 0.5f);
+  levels = L;
+  return CURVIS_OK;
+}
+/* the chains of both skies, built on first use (a render call with the option on, curvis_ctx_sky_mip_level) */
+int ensure_sky_mips(curvis_ctx *ctx, int which) {
+  SkyTexture &S = ctx->sky[which];
+  if (!S.texels) return fail(ctx, CURVIS_E_NO_SKY, "sky not set");
+  if (S.mip_levels) return CURVIS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int rc = build_sky_mips(ctx, (const unsigned *)S.texels, S.w, S.h, S.mip_texels, S.mip_table, S.mip_host, S.mip_levels);
+  if (rc) S.drop_mips();
+  return rc;
+}
+SkyMipArgs sky_mip_args(const curvis_ctx *ctx) {
+  SkyMipArgs A;
+  for (int k = 0; k < 2; ++k) A.tab[k] = ctx->sky[k].mip_table.p, A.levels[k] = ctx->sky[k].mip_levels;
+  return A;
+}
+
 /* workgroup size of the static and relay kernels ("block_threads"; total_rays is a multiple of 64) */
 unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
   (void)kind;
@@ -505,8 +574,9 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
  * more. */
 template <int KIND, bool PHI, bool FAST, int SS, int FILTER, int PROJ, int ADAPT = 0>
 int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused, int relay) {
+  static_assert(!(PHI && FILTER == 2), "the debug dump's staged kernel has no mip-mapped lookup: render_impl refuses the call");
   const IntegrateParams &P = PA; /* what every kernel but the ADAPT ones takes */
-  if constexpr (ADAPT == 0) /* scaled steps and Heun steps never take the relay kernel (choose_render_path) */
+  if constexpr (ADAPT == 0 && FILTER != 2) /* scaled steps, Heun steps and the mip-mapped lookup never take the relay kernel (choose_render_path) */
     if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, P, relay == 2);
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const dim3 grid((unsigned)((P.total_rays + bt - 1ull) / bt));
@@ -534,9 +604,18 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused
       staged = true;
     }
   }
-  if constexpr (ADAPT != 0 && !PHI) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ, ADAPT>), grid, dim3(bt), 0, ctx->stream, PA);
-  if constexpr (ADAPT == 0)
-    if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ>), grid, dim3(bt), 0, ctx->stream, P);
+  if constexpr (FILTER == 2) { /* option "sky_mipmap": the fused kernel alone, its argument with the level tables appended */
+    if constexpr (!PHI) {
+      WithSkyMip<IntegrateArgs<ADAPT>> PM;
+      static_cast<IntegrateArgs<ADAPT> &>(PM) = PA;
+      PM.mip = sky_mip_args(ctx);
+      hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, 2, PROJ, ADAPT>), grid, dim3(bt), 0, ctx->stream, PM);
+    }
+  } else {
+    if constexpr (ADAPT != 0 && !PHI) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ, ADAPT>), grid, dim3(bt), 0, ctx->stream, PA);
+    if constexpr (ADAPT == 0)
+      if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ>), grid, dim3(bt), 0, ctx->stream, P);
+  }
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
@@ -631,8 +710,9 @@ RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
                                                                    : 4ull * (unsigned long long)ctx->prop.multiProcessorCount;
   const size_t relay_staging = (size_t)tiles * 64u * kStoreBytesPerPixel;
   /* option "step_scale": the static kernel -- the relay segments are sized in fixed-delta steps and its hand-over pattern was tuned on
-   * fixed-delta step counts.  Option "integrator" = 1 likewise: there is no relay form of the Heun step */
-  p.relay = !c.adapt && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
+   * fixed-delta step counts.  Option "integrator" = 1 likewise: there is no relay form of the Heun step.  Option "sky_mipmap" = 1: no relay
+   * form either (the epilogue is not where a single frame's time goes) */
+  p.relay = !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
             relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
   p.chunk = c.n_frames;
   p.store_bytes = p.relay ? relay_staging : 0;
@@ -914,7 +994,14 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
                   "Photon already beyond the maximum radius. Cannot evaluate escape. (src/systems.rs:122-124)");
   }
   if (!ctx->sky[0].texels || !ctx->sky[1].texels) return fail(ctx, CURVIS_E_NO_SKY, "both background images must be set");
+  /* option "sky_mipmap": rays are paired in 2 x 2 quads of FRAME coordinates, whatever the split into bands: a band begins on an even
+   * row of the ray grid and holds an even number of them unless it ends the frame */
+  if (c.filter == 2u && band && ((c.row_begin & 1u) || ((c.row_count & 1u) && c.row_begin + c.row_count != H_full)))
+    return fail(ctx, CURVIS_E_INVALID, "sky_mipmap = 1: a row band must begin on an even row and hold an even number of rows unless it ends the frame");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (c.filter == 2u)
+    for (int k = 0; k < 2; ++k)
+      if ((rc = ensure_sky_mips(ctx, k))) return rc;
 
   c.npix = (size_t)(c.W / c.ss) * (c.H / c.ss);
   c.fb_bytes = c.npix * 3 * c.n_frames;
@@ -975,35 +1062,38 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
   BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u, 0u};
-  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->projection && !ctx->step_scale && !ctx->integrator)) return render_rays(ctx, c);
+  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->sky_mipmap && !ctx->projection && !ctx->step_scale && !ctx->integrator)) return render_rays(ctx, c);
   /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under
    * the name of the projection when it is on, else of the filter when that is on, else of the supersampling when that is on.  The scaled
    * steps (option "step_scale") exist in the fused kernels and in the debug dump's: a shape with a message of its own in the last
    * column is refused under the option's name when none of the other three refuses it.  The option's fourth refusal, fast_math = 0,
    * holds for all three renderers and is therefore made where they all pass, in step_scale_kappa (prepare_call_shape).  The Heun step
    * (option "integrator" = 1) exists in the same kernels as the scaled steps and is refused for the same shapes, under its own name
-   * when "step_scale" is off. */
-  const bool f = ctx->sky_filter != 0, p = ctx->projection != 0, n = ctx->supersample > 1, a = ctx->step_scale != 0, h = ctx->integrator != 0;
+   * when "step_scale" is off.  The mip-mapped lookup (option "sky_mipmap" = 1) is refused for the filter's three shapes under its own
+   * name, before the others. */
+  const bool m = ctx->sky_mipmap != 0, f = ctx->sky_filter != 0, p = ctx->projection != 0, n = ctx->supersample > 1, a = ctx->step_scale != 0, h = ctx->integrator != 0;
   const struct {
     bool refused;
-    const char *projection, *filter, *supersample, *step_scale, *integrator;
+    const char *mipmap, *projection, *filter, *supersample, *step_scale, *integrator;
   } shapes[3] = {
-      {dbg_out != nullptr, "projection != 0: the debug dump replays the perspective camera (set projection = 0)",
+      {dbg_out != nullptr, "sky_mipmap = 1: the debug dump records the nearest lookup (set sky_mipmap = 0)", "projection != 0: the debug dump replays the perspective camera (set projection = 0)",
        "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)",
        "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)", nullptr, nullptr},
-      {ctx->variant == 0, "projection != 0: variant = 0 (the persistent kernel) has the perspective camera only",
+      {ctx->variant == 0, "sky_mipmap = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
+       "projection != 0: variant = 0 (the persistent kernel) has the perspective camera only",
        "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
        "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve",
        "step_scale != 0: variant = 0 (the persistent kernel) takes the reference's fixed step only",
        "integrator = 1: variant = 0 (the persistent kernel) takes the reference's Euler step only"},
-      {ctx->fuse_shade == 0, "projection != 0: fuse_shade = 0 (the unfused static kernel) has the perspective camera only",
+      {ctx->fuse_shade == 0, "sky_mipmap = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
+       "projection != 0: fuse_shade = 0 (the unfused static kernel) has the perspective camera only",
        "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
        "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve",
        dbg_out ? nullptr : "step_scale != 0: fuse_shade = 0 (the unfused static kernel) takes the reference's fixed step only outside the debug dump",
        dbg_out ? nullptr : "integrator = 1: fuse_shade = 0 (the unfused static kernel) takes the reference's Euler step only outside the debug dump"}};
   for (const auto &s : shapes)
     if (s.refused) {
-      const char *why = p ? s.projection : f ? s.filter : n ? s.supersample : nullptr;
+      const char *why = m ? s.mipmap : p ? s.projection : f ? s.filter : n ? s.supersample : nullptr;
       if (!why && a) why = s.step_scale;
       if (!why && h) why = s.integrator;
       if (why) return fail(ctx, CURVIS_E_INVALID, why);

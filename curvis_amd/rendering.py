@@ -135,16 +135,20 @@ class ImageRenderingSystem:
     lookup) blends the four sky texels around every ray's direction; projection="equirectangular" or "fisheye" (not in the reference;
     "perspective" is its camera) renders a 360-degree or a dome frame (library option "projection"); step_scale=L0 (not in the
     reference; 0 is its fixed step) lets the Euler step grow as |l| / L0 outside the distance L0 (library option "step_scale"); integrator="heun" (not in the
-    reference; "euler" is its loop) integrates with Heun's method, two Euler steps averaged (library option "integrator")."""
+    reference; "euler" is its loop) integrates with Heun's method, two Euler steps averaged (library option "integrator");
+    sky_mipmap=True (not in the reference; needs sky_filter="bilinear") takes the blend on a mip pyramid of the sky (library option
+    "sky_mipmap")."""
 
     def __init__(self, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-                 projection="perspective", step_scale=0.0, integrator="euler"):
+                 projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
         from .images import load_image_as_spherical_image
-        from .systems import RelativisticSystem, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
+        from .systems import RelativisticSystem, check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
         check_step_scale(step_scale)
         self.step_scale = step_scale
         check_integrator(integrator)
         self.integrator = integrator
+        check_sky_mipmap(sky_mipmap)
+        self.sky_mipmap = sky_mipmap
         self.supersample = check_supersample(supersample)
         check_sky_filter(sky_filter)
         self.sky_filter = sky_filter
@@ -160,10 +164,10 @@ class ImageRenderingSystem:
 
     @classmethod
     def new(cls, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-            projection="perspective", step_scale=0.0, integrator="euler"):
+            projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
         """ImageRenderingSystem::new(metric, image_rendering_settings) (src/rendering.rs:33-70)"""
         return cls(metric, image_rendering_settings, context=context, mode=mode, supersample=supersample, sky_filter=sky_filter,
-                   projection=projection, step_scale=step_scale, integrator=integrator)
+                   projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap)
 
     def render(self):
         import os
@@ -179,13 +183,13 @@ class ImageRenderingSystem:
             image = self.relativistic_system.render_image(st.max_iterations_propagation, st.escape_radius, st.ray_integration_step,
                                                           supersample=self.supersample, sky_filter=self.sky_filter,
                                                           projection=self.projection, step_scale=self.step_scale,
-                                                          integrator=self.integrator)
+                                                          integrator=self.integrator, sky_mipmap=self.sky_mipmap)
         else:
             image = self.relativistic_system.render_image_efficient(
                 st.max_iterations_propagation, st.escape_radius, st.ray_integration_step, st.alphas_num,
                 st.max_iterations_sampling, st.sampling_convergence_threshold_1, st.sampling_convergence_threshold_2,
                 supersample=self.supersample, sky_filter=self.sky_filter, projection=self.projection, step_scale=self.step_scale,
-                integrator=self.integrator)
+                integrator=self.integrator, sky_mipmap=self.sky_mipmap)
         path_of_image = os.path.join(folder, os.path.splitext(st.output_image_name)[0] + ".png")
         save_image(path_of_image, image)
         return path_of_image
@@ -215,15 +219,19 @@ class VideoRenderingSystem:
     the reference; "nearest" is its lookup) blends the four sky texels around every ray's direction.  projection="equirectangular" or
     "fisheye" (not in the reference; "perspective" is its camera): library option "projection" on every frame.  step_scale=L0 (not in
     the reference; 0 is its fixed step): library option "step_scale" on every frame.  integrator="heun" (not in the reference;
-    "euler" is its loop): library option "integrator" on every frame, the prefetch included."""
+    "euler" is its loop): library option "integrator" on every frame, the prefetch included.  sky_mipmap=True (not in the reference;
+    needs sky_filter="bilinear"): library option "sky_mipmap" on every frame -- the blend on a mip pyramid of the sky, which lowers the
+    frame-to-frame flicker of the strongly minified secondary images (measured in profiles/sky_mipmap_quality.txt)."""
 
     def __init__(self, metric, context, interpolator, frame_rate, resolution, camera_diagonal, camera_focal_length,
                  escape_radius, max_iterations_propagation, ray_integration_step, rank=0, world_size=1, batch=8,
                  mode="efficient", sampling_initial_nums=100, sampling_convergence_threshold_1=1e-5, supersample=1,
-                 sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler"):
-        from .systems import check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
+                 sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
+        from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
         self._step_scale = check_step_scale(step_scale)
         self.step_scale = step_scale
+        self._sky_mipmap = check_sky_mipmap(sky_mipmap)
+        self.sky_mipmap = sky_mipmap
         self._integrator = check_integrator(integrator)
         self.integrator = integrator
         if mode not in ("efficient", "brute"):
@@ -250,14 +258,15 @@ class VideoRenderingSystem:
 
     @classmethod
     def new(cls, metric, video_rendering_settings, context=None, rank=0, world_size=1, batch=8, mode="efficient", supersample=1,
-            sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler"):
+            sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
         """VideoRenderingSystem::new(metric, video_rendering_settings) (src/rendering.rs:188-221): loads the two
         backgrounds into the context's HBM and the camera path into an Interpolator.  The reference passes
         `alphas_num` and `max_iterations_sampling` separately and `sampling_convergence_threshold_1` twice (:299-307);
         so does this (threshold_2 of the settings is never read, as there)."""
         from .images import load_image_as_spherical_image
-        from .systems import check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context
+        from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context
         check_supersample(supersample)  # before the context and the files are touched
+        check_sky_mipmap(sky_mipmap)
         check_step_scale(step_scale)
         check_integrator(integrator)
         check_sky_filter(sky_filter)
@@ -271,7 +280,7 @@ class VideoRenderingSystem:
                    st.max_iterations_propagation, st.ray_integration_step, rank=rank, world_size=world_size, batch=batch,
                    mode=mode, sampling_initial_nums=st.alphas_num,
                    sampling_convergence_threshold_1=st.sampling_convergence_threshold_1, supersample=supersample,
-                   sky_filter=sky_filter, projection=projection, step_scale=step_scale, integrator=integrator)
+                   sky_filter=sky_filter, projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap)
         self.max_iterations_sampling = int(st.max_iterations_sampling)
         self.video_rendering_settings = st
         return self
@@ -327,10 +336,10 @@ class VideoRenderingSystem:
 
     def _render_batch(self, cams, download):
         if (getattr(self, "supersample", 1) != 1 or getattr(self, "_sky_filter", 0) != 0 or getattr(self, "_projection", 0) != 0
-                or getattr(self, "_step_scale", 0) != 0 or getattr(self, "_integrator", 0) != 0):
+                or getattr(self, "_step_scale", 0) != 0 or getattr(self, "_integrator", 0) != 0 or getattr(self, "_sky_mipmap", 0) != 0):
             from .systems import _Supersampled
             with _Supersampled(self.context, getattr(self, "supersample", 1), getattr(self, "_sky_filter", 0),
-                               getattr(self, "_projection", 0), getattr(self, "_step_scale", 0), getattr(self, "_integrator", 0)):
+                               getattr(self, "_projection", 0), getattr(self, "_step_scale", 0), getattr(self, "_integrator", 0), getattr(self, "_sky_mipmap", 0)):
                 return self._render_batch_as_set(cams, download)
         return self._render_batch_as_set(cams, download)
 
@@ -351,12 +360,12 @@ class VideoRenderingSystem:
             thr1 = self.sampling_convergence_threshold_1
             args = (self.metric, cams, self.max_iterations_propagation, self.escape_radius, self.ray_integration_step,
                     self.sampling_initial_nums, getattr(self, "max_iterations_sampling", self.sampling_initial_nums), thr1, thr1)
-            if getattr(self, "_step_scale", 0) != 0 or getattr(self, "_integrator", 0) != 0:
+            if getattr(self, "_step_scale", 0) != 0 or getattr(self, "_integrator", 0) != 0 or getattr(self, "_sky_mipmap", 0) != 0:
                 # "step_scale" and "integrator" are part of what identifies a sampler job: a prefetch made under another value is
-                # never consumed
+                # never consumed ("sky_mipmap" is set here as around the render calls, though the samplers never see a sky)
                 from .systems import _Supersampled
                 with _Supersampled(self.context, getattr(self, "supersample", 1), getattr(self, "_sky_filter", 0),
-                                   getattr(self, "_projection", 0), getattr(self, "_step_scale", 0), getattr(self, "_integrator", 0)):
+                                   getattr(self, "_projection", 0), getattr(self, "_step_scale", 0), getattr(self, "_integrator", 0), getattr(self, "_sky_mipmap", 0)):
                     self.context.prefetch_efficient(*args)
             else:
                 self.context.prefetch_efficient(*args)

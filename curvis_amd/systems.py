@@ -686,6 +686,26 @@ class Context:
                                                  taps.ctypes.data_as(C.POINTER(C.c_uint32)), rgb.ctypes.data), self._h)
         return taps, rgb
 
+    def sky_mip_level(self, which, level):
+        """level `level` of the mip chain of sky `which` (library option "sky_mipmap"; built if need be) as an h x w x 4 uint8 array
+        (curvis_ctx_sky_mip_level)"""
+        w, h = C.c_uint32(), C.c_uint32()
+        check(lib().curvis_ctx_sky_mip_level(self._h, which, level, None, C.byref(w), C.byref(h)), self._h)
+        out = np.zeros((h.value, w.value, 4), dtype=np.uint8)
+        check(lib().curvis_ctx_sky_mip_level(self._h, which, level, out.ctypes.data, C.byref(w), C.byref(h)), self._h)
+        return out
+
+    def selftest_sky_mip(self, rgba, triples):
+        """the per-ray colour of library option "sky_mipmap" as the kernels compile it, on n (Xc, Yc, rho) triples (n x 3 uint32) over
+        the mip chain of the h x w x 4 uint8 image `rgba`: rgb uint8 [n, 3] (curvis_selftest_sky_mip)"""
+        img = np.ascontiguousarray(rgba, dtype=np.uint8)
+        assert img.ndim == 3 and img.shape[2] == 4
+        t = np.ascontiguousarray(triples, dtype=np.uint32).reshape(-1, 3)
+        rgb = np.zeros((t.shape[0], 3), dtype=np.uint8)
+        check(lib().curvis_selftest_sky_mip(self._h, img.shape[1], img.shape[0], img.ctypes.data, t.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            t.shape[0], rgb.ctypes.data), self._h)
+        return rgb
+
 
 _default_ctx = {}
 
@@ -766,6 +786,13 @@ def check_sky_filter(sky_filter):
     return SKY_FILTERS.index(sky_filter)
 
 
+def check_sky_mipmap(sky_mipmap):
+    """the mip-mapped lookup as the library option's value (0 or 1), or ValueError: only a bool is accepted"""
+    if not isinstance(sky_mipmap, bool):
+        raise ValueError("sky_mipmap must be False or True")
+    return int(bool(sky_mipmap))
+
+
 PROJECTIONS = ("perspective", "equirectangular", "fisheye")  # the values of library option "projection", 0, 1 and 2
 
 
@@ -804,12 +831,12 @@ def check_integrator(integrator):
 
 class _Supersampled:
     """the context's "supersample" option set to `factor` -- and "sky_filter" to `sky_filter` (0 or 1), "projection" to `projection`
-    (0, 1 or 2), "step_scale" to `step_scale` (the integer S), "integrator" to `integrator` (0 or 1) -- for the duration of a render
-    call, then put back"""
+    (0, 1 or 2), "step_scale" to `step_scale` (the integer S), "integrator" to `integrator` (0 or 1), "sky_mipmap" to `sky_mipmap` (0 or
+    1) -- for the duration of a render call, then put back"""
 
-    def __init__(self, context, factor, sky_filter=0, projection=0, step_scale=0, integrator=0):
+    def __init__(self, context, factor, sky_filter=0, projection=0, step_scale=0, integrator=0, sky_mipmap=0):
         self.context, self.want = context, (("supersample", factor), ("sky_filter", sky_filter), ("projection", projection),
-                                            ("step_scale", step_scale), ("integrator", integrator))
+                                            ("step_scale", step_scale), ("integrator", integrator), ("sky_mipmap", sky_mipmap))
 
     def __enter__(self):
         self.before = [self.context.get_option(key) for key, _ in self.want]
@@ -832,7 +859,8 @@ class RelativisticSystem:
     "projection"); and step_scale=L0 (not in the reference; 0, the default, is its fixed step): outside the coordinate distance L0, a
     multiple of 1/256, a ray's Euler step grows as |l| / L0 (library option "step_scale"); and integrator="euler" (the reference's
     forward Euler) or "heun" (not in the reference: Heun's method, second order, two Euler steps averaged; library option
-    "integrator")."""
+    "integrator"); and sky_mipmap (False or True; not in the reference: with sky_filter="bilinear", the blend is taken on a mip
+    pyramid of the sky at the level of the ray's footprint among its neighbours; library option "sky_mipmap")."""
 
     def __init__(self, metric, background_positive, background_negative, camera, context=None):
         self.metric = metric
@@ -850,12 +878,12 @@ class RelativisticSystem:
             ctx.set_sky(1, self.background_negative)
 
     def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
-                     step_scale=0.0, integrator="euler"):
+                     step_scale=0.0, integrator="euler", sky_mipmap=False):
         """The per-pixel renderer; returns an HxWx3 uint8 array (DynamicImage::ImageRgb8)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
-        scale, heun = check_step_scale(step_scale), check_integrator(integrator)
+        scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale, heun):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
             rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
         self.last_stats = st
         return rgb
@@ -863,12 +891,12 @@ class RelativisticSystem:
     def render_image_efficient(self, max_iterations_propagation, max_radius, delta, alpha_nums,
                                max_iterations_sampling, sampling_convergence_threshold_1,
                                sampling_convergence_threshold_2, supersample=1, sky_filter="nearest", projection="perspective",
-                               step_scale=0.0, integrator="euler"):
+                               step_scale=0.0, integrator="euler", sky_mipmap=False):
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
-        scale, heun = check_step_scale(step_scale), check_integrator(integrator)
+        scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale, heun):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
             rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
                                                     alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
                                                     sampling_convergence_threshold_2)
@@ -876,13 +904,13 @@ class RelativisticSystem:
         return rgb
 
     def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
-                            step_scale=0.0, integrator="euler"):
+                            step_scale=0.0, integrator="euler", sky_mipmap=False):
         """NOT in the reference: the image render_image_efficient approximates, with compute_escape_angle evaluated
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
-        scale, heun = check_step_scale(step_scale), check_integrator(integrator)
+        scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale, heun):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
             rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
         self.last_stats = st
         return rgb

@@ -114,7 +114,8 @@ int curvis_ctx_device_status(const curvis_ctx *ctx, char *pci_bus_id, size_t cap
  * row-major, host memory; it is copied to HBM and kept for all frames. */
 int curvis_ctx_set_sky(curvis_ctx *ctx, int which, const uint8_t *rgba, uint32_t w, uint32_t h);
 /* same, from a device pointer on this context's GPU (e.g. a buffer filled by an RCCL broadcast);
- * copy != 0 copies it, copy == 0 borrows it (caller keeps it alive). */
+ * copy != 0 copies it, copy == 0 borrows it (caller keeps it alive).  With option "sky_mipmap" a borrowed buffer is level 0 of the
+ * mip chain, whose other levels are built from it once: a caller who rewrites the buffer calls this function again. */
 int curvis_ctx_set_sky_device(curvis_ctx *ctx, int which, const void *dev_rgba, uint32_t w, uint32_t h, int copy);
 /* SphericalImage::set_forward_up (src/images.rs:102-104); default forward = x, up = z. */
 int curvis_ctx_set_sky_orientation(curvis_ctx *ctx, int which, const double forward[3], const double up[3]);
@@ -140,6 +141,10 @@ int curvis_rccl_comm_destroy(void *nccl_comm);
 /* Read back `bytes` bytes at byte offset `offset` of sky texture `which` from HBM (e.g. to verify on every rank that
  * a broadcast texture equals the root's file). */
 int curvis_ctx_read_sky(curvis_ctx *ctx, int which, size_t offset, size_t bytes, uint8_t *out);
+/* Level `level` of the mip chain of sky `which` (option "sky_mipmap" below; level 0 is the sky), built on the context's stream if it
+ * is not there yet: *w x *h RGBA8 texels into `out` (NULL: the size alone).  CURVIS_E_NO_SKY without a sky, CURVIS_E_INVALID for a
+ * level the chain does not have.  For tests and tools. */
+int curvis_ctx_sky_mip_level(curvis_ctx *ctx, int which, uint32_t level, uint8_t *out, uint32_t *w, uint32_t *h);
 
 /* how two devices of this node are connected (hipExtGetLinkTypeAndHopCount, hipDeviceCanAccessPeer, hipDeviceGetP2PAttribute):
  * link_type = HSA_AMD_LINK_INFO_TYPE_* (2 PCIe, 4 xGMI; 0 with hops 0 for a == b; -1 unknown).  Read beside the measured
@@ -218,6 +223,20 @@ int curvis_sky_texel_index(uint32_t w, uint32_t h, const double inv_rot[9], cons
  * and CURVIS_E_INVALID for w or h beyond 2^23 (raw set, taps zero: 256 w is no u32 any more). */
 int curvis_sky_bilinear_taps(uint32_t w, uint32_t h, const double inv_rot[9], const double v[3], uint32_t taps[6] /* x0 x1 y0 y1 fx fy */,
                              uint32_t raw[2] /* X>>8, Y>>8 */);
+/* The integer parts of option "sky_mipmap" on the host (the option's paragraph below has the definition; the kernels compile the same
+ * text).  curvis_sky_mip_rho: the footprint of a ray at own = {Xc, Yc} on a sky w texels wide from its horizontal and vertical quad
+ * partners' {Xc', Yc'}; a partner with ok = 0 contributes nothing.  curvis_sky_mip_level: level k and fraction f for a pyramid of
+ * `levels` levels.  curvis_sky_mip_taps: steps 3-4 of the bilinear definition on level `level` of a w x h sky for (xc >> level,
+ * yc >> level) -- taps = {x0, x1, y0, y1, fx, fy}, size = {w_level, h_level}.  curvis_sky_mip_mix: the blend of two packed RGBA8 level
+ * colours.  curvis_sky_mip_pyramid: level `level` of the pyramid of a host image (out may be NULL: the size alone).  All return
+ * CURVIS_OK, or CURVIS_E_INVALID for a null pointer, an empty or too large sky, a level the pyramid does not have, f > 255 or an index
+ * outside the virtual sky. */
+int curvis_sky_mip_rho(uint32_t w, const uint32_t own[2], const uint32_t horizontal[2], int32_t horizontal_ok, const uint32_t vertical[2],
+                       int32_t vertical_ok, uint32_t *rho);
+int curvis_sky_mip_level(uint32_t rho, uint32_t levels, uint32_t *k, uint32_t *f);
+int curvis_sky_mip_taps(uint32_t w, uint32_t h, uint32_t level, uint32_t xc, uint32_t yc, uint32_t taps[6], uint32_t size[2]);
+int curvis_sky_mip_mix(uint32_t ck, uint32_t ck1, uint32_t f, uint32_t *out);
+int curvis_sky_mip_pyramid(const uint8_t *rgba, uint32_t w, uint32_t h, uint32_t level, uint8_t *out, uint32_t *wl, uint32_t *hl);
 
 /* A band of image rows [row_begin, row_begin + row_count) of the same frame: rays are independent
  * (src/systems.rs:316-326), so a single image can be split across GPUs by rows and assembled on the host
@@ -427,6 +446,33 @@ int curvis_ctx_download_wait(curvis_ctx *ctx);
  * the N x N box average is taken over the filtered colours.  A render call with the filter on and a sky wider or taller than 2^23
  * texels fails with CURVIS_E_INVALID (256 w must stay a u32); so do, as under supersampling, curvis_render_brute_debug,
  * "variant" = 0 and "fuse_shade" = 0.  Sampler prefetch, PNG front end, downloads, row bands and batches are untouched),
+ * "sky_mipmap" (0 = off, the default, or 1; anything else is refused with CURVIS_E_INVALID and the old value stays.  It acts on top of
+ * the bilinear filter: setting it is always allowed, in either order with "sky_filter", and a render call with "sky_mipmap" = 1 and
+ * "sky_filter" = 0 fails with CURVIS_E_INVALID.  With 0 nothing changes.  With 1:
+ *   Pyramid.  Level 0 is the sky T0 of w x h texels.  Level k+1 has w_{k+1} = (w_k + 1) >> 1 by h_{k+1} = (h_k + 1) >> 1 texels, and
+ *     T_{k+1}[y][x] is, per colour channel, (a + b + c + d + 2) >> 2 of the four values of level k at columns 2x and
+ *     min(2x + 1, w_k - 1), rows 2y and min(2y + 1, h_k - 1); alpha is 255.  One rounding per level, half up.  There are
+ *     L = 1 + ceil(log2(max(w, h))) levels, the last of 1 x 1.  Where a size is odd the last column or row counts its source twice:
+ *     the definition is this recurrence, not an area average.
+ *   Footprint.  Rays are paired in 2 x 2 quads of absolute ray coordinates: the partners of ray (px, py) are (px ^ 1, py) and
+ *     (px, py ^ 1) -- coordinates of the fine grid under "supersample", of the frame (not of the band) in a row band.  For a ray that
+ *     escaped to sky s, with the (Xc, Yc) of step 2 of "sky_filter", each partner contributes dX = |wrap(Xc' - Xc)|, where wrap
+ *     reduces modulo 256 w into [-128 w, 128 w), and dY = |Yc' - Yc|; a partner outside the frame, capped (black) or escaped to the
+ *     other sky contributes nothing.  rho is the largest of the up to four contributions, 0 without any.
+ *   Level.  rho < 256: k = 0, f = 0.  Otherwise k = msb(rho) - 8 and f = (rho >> k) & 255.  Then, if k >= L - 1: k = L - 1, f = 0
+ *     (a render never gets there, since rho <= max(128 w, 256 h - 1); it makes the function total).
+ *   Colour.  c_k is steps 3-5 of "sky_filter" applied to T_k with w_k, h_k, X_k = Xc >> k and Y_k = Yc >> k (X_k < 256 w_k always
+ *     holds); level 0 is the "sky_filter" = 1 colour bit for bit.  f = 0: the colour is c_k.  Otherwise, per channel,
+ *     out = ((256 - f) c_k + f c_{k+1} + 128) >> 8.
+ * Counters, n_oob, the nearest lookup's tx and ty are unchanged, capped rays stay black, and the "supersample" box average is taken
+ * over the mip-filtered sub-ray colours.  Row bands: so that the quads do not depend on how a frame is split, a band of
+ * curvis_render_brute_rows must, in rows of the ray grid, begin on an even row and hold an even number of rows unless it ends on the
+ * frame's last row; otherwise the call fails with CURVIS_E_INVALID (with "supersample" > 1 every band of output rows qualifies).
+ * Refused with CURVIS_E_INVALID while it is 1, as under "sky_filter": curvis_render_brute_debug, "variant" = 0 and "fuse_shade" = 0.
+ * The levels above 0 (a third of the sky's bytes) belong to the context's sky; they are built on the context's stream by the first
+ * render call with the option on -- a context that never sets it allocates nothing -- and dropped by curvis_ctx_set_sky,
+ * curvis_ctx_set_sky_device and curvis_ctx_bcast_skies (every device rebuilds its own chain).  The relay kernel is not used while the
+ * option is on),
  * "projection" (0 = perspective, the default and the reference's mapping bit for bit, 1 = equirectangular, 2 = equidistant fisheye;
  * anything else is refused with CURVIS_E_INVALID and the old value stays.  It replaces only the three expressions that form the
  * un-normalised camera-space vector vec = (x, y, z) of a pixel (camera axes as in the reference: x forward, y left, z up); everything
@@ -501,7 +547,10 @@ int curvis_ctx_download_wait(curvis_ctx *ctx);
  * way; a table that outgrows the kernel's fixed arrays -- 1536 samples -- sends the call to the host-paced sampler;
  * "sampling_speculation" = 0 switches speculation off on the device too); read-only after an efficient render:
  * "last_sampling_launches", "last_sampling_evaluated", "last_sampler_path" (0 host-paced, 1 device, 2 device fell back to the
- * host), "last_sampling_chains" (device: Euler chains the slowest job waited for); after any render: "last_frames"; after a relay render: "last_relay_launches",
+ * host), "last_sampling_chains" (device: Euler chains the slowest job waited for), "last_pixel_tiled" (1 when the per-pixel launch
+ * enumerated pixels by 8x8 tiles -- "supersample" > 1, "sky_mipmap" = 1, or the measurement switch "pixel_tiled" = 1, which asks for
+ * that enumeration where the linear kernel would do: same frames, same counters --, else 0); after a mip chain build:
+ * "last_sky_mip_build_us" (HIP-event time of its launches), after curvis_ctx_set_sky_device with copy != 0: "last_sky_copy_us"; after any render: "last_frames"; after a relay render: "last_relay_launches",
  * "last_relay_parks".  Relay safety net: if a relay launch reports waves that gave up waiting (the kernel leans
  * on in-order workgroup dispatch, which HIP does not promise), the frame is rendered again by the static kernel and
  * "relay_disabled" becomes 1 for the context ("relay_fallbacks" counts such renders); "relay_verify" = 1 (debug)
@@ -550,6 +599,11 @@ int curvis_selftest_sky_indices(curvis_ctx *ctx, uint32_t w, uint32_t h, const d
  * reciprocals, as in curvis_selftest_sky_indices).  tests/test_gpu_sky_filter.py. */
 int curvis_selftest_sky_bilinear(curvis_ctx *ctx, uint32_t w, uint32_t h, const double inv_rot[9], const uint8_t *rgba, const double *dirs,
                                  size_t n, uint32_t *out_taps, uint8_t *out_rgb);
+
+/* the per-ray colour of option "sky_mipmap" = 1 as the kernels compile it: rgba is a HOST image of w x h RGBA8 texels, whose mip chain
+ * is built on the device; triples = n x {Xc, Yc, rho} (Xc, Yc beyond the virtual sky are clamped into it); out_rgb: n x {r, g, b}.  The
+ * function has no floating-point part, so there is one instantiation.  tests/test_gpu_sky_mipmap.py. */
+int curvis_selftest_sky_mip(curvis_ctx *ctx, uint32_t w, uint32_t h, const uint8_t *rgba, const uint32_t *triples, size_t n, uint8_t *out_rgb);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,9 @@ of each.  Needs no GPU.
 A kernel's text is everything between its label and its .Lfunc_end label, with the assembler's function-local label numbers
 (.LBB<n>_, .Lfunc_end<n>, .Ltmp<n>) renumbered: they count the functions of the file and shift when one is added.  A kernel
 template that gained a trailing template parameter is compared, in its instantiation with that parameter at its default (1 for a
-factor, 0 for a switch), with its old self; so is a kernel that became a template with one such parameter.
+factor, 0 for a switch), with its old self; so is a kernel that became a template with one such parameter, and one whose argument
+type is spelled differently (such a kernel has a NEW mangled symbol with the old instructions: a profile or a rocprof filter keyed on
+the full signature no longer matches it, one keyed on the name and template arguments does).
 Exit status 1 when a kernel present on both sides differs."""
 import argparse
 import difflib
@@ -72,6 +74,13 @@ def main():
     # (names are paired without their parameter lists: the type of a kernel's argument may be spelled through the new parameter)
     head = lambda d: d.replace("(anonymous namespace)::", "").split("(")[0] + "("  # noqa: E731
     old_of = {head(names[n]): n for n in b0}
+    # a kernel whose argument type alone is spelled differently (through a template parameter it already had): the same name in front
+    # of the parameter list
+    for n in [n for n in b1 if n not in b0]:
+        was = old_of.get(head(names[n]))
+        if was is not None and was not in b1:
+            b1[was], u1[was] = b1.pop(n), u1.pop(n, {})
+            names[was] = names.pop(n)
     for pattern, to in ((r", 0>\(", ">("), (r"^void (.*)<0>\(", r"\1("), (r", 1>\(", ">(")):
         for n in [n for n in b1 if n not in b0 and re.search(pattern, head(names[n]))]:
             was = old_of.get(re.sub(pattern, to, head(names[n]), count=1))
