@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libcurvis_hip.so")
 
 OK = 0
 E_INVALID, E_NO_DEVICE, E_HIP, E_CAMERA_OUTSIDE, E_NO_SKY, E_PARALLEL, E_METRIC, E_RCCL, E_SAMPLING, E_IO = range(-1, -11, -1)
-METRIC_ELLIS, METRIC_INTERSTELLAR, METRIC_FLAT = 0, 1, 2
+METRIC_ELLIS, METRIC_INTERSTELLAR, METRIC_FLAT, METRIC_SCHWARZSCHILD = 0, 1, 2, 3
 RCCL_ID_BYTES = 128
 
 
@@ -69,6 +69,9 @@ SYMBOLS = {
     "curvis_orientation_init": (C.c_int, [_dp, _dp, _dp, _dp, _dp]),
     "curvis_metric_validate": (C.c_int, [C.POINTER(Metric)]),
     "curvis_metric_functions": (C.c_int, [C.POINTER(Metric), C.c_double, _dp, _dp, _dp]),
+    "curvis_schwarzschild_u": (C.c_int, [C.POINTER(Metric), C.c_double, _dp]),
+    "curvis_walk_ray": (C.c_int, [C.POINTER(Metric), _dp, _dp, C.c_double, C.c_int64, C.c_int32, C.c_uint32, C.c_double,
+                                  C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "curvis_metric_tensor": (C.c_int, [C.POINTER(Metric), _dp, _dp, _dp]),
     "curvis_camera_outward_vector": (C.c_int, [C.POINTER(CameraC), C.c_uint32, C.c_uint32, _dp, _dp]),
     "curvis_camera_outward_vector_projected": (C.c_int, [C.POINTER(CameraC), C.c_int32, C.c_uint32, C.c_uint32, _dp, _dp]),

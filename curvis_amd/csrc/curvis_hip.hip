@@ -477,6 +477,8 @@ int curvis_metric_validate(const curvis_metric *m) {
       return CURVIS_OK;
     case CURVIS_METRIC_FLAT:
       return CURVIS_OK;
+    case CURVIS_METRIC_SCHWARZSCHILD: /* the mass in m; rho and a are ignored */
+      return (m->m > 0.0) ? CURVIS_OK : CURVIS_E_METRIC; /* false for a NaN */
     default:
       return CURVIS_E_METRIC;
   }
@@ -491,6 +493,13 @@ int curvis_metric_functions(const curvis_metric *m, double l, double *r, double 
   if (r) *r = rr;
   if (r_squared) *r_squared = r2;
   if (r_derivative) *r_derivative = rd;
+  return CURVIS_OK;
+}
+
+int curvis_schwarzschild_u(const curvis_metric *m, double l, double *u) {
+  if (!m || !u || m->kind != CURVIS_METRIC_SCHWARZSCHILD) return CURVIS_E_INVALID;
+  if (curvis_metric_validate(m) != CURVIS_OK) return CURVIS_E_METRIC;
+  *u = cvk::schwarzschild_u(make_metric(*m), l);
   return CURVIS_OK;
 }
 
@@ -585,6 +594,36 @@ int curvis_heun_step(const curvis_metric *metric, double x[4], double p_cov[4], 
   if (curvis_metric_validate(metric) != CURVIS_OK) return CURVIS_E_METRIC;
   const cvk::MetricParams MP = make_metric(*metric);
   with_kind(metric->kind, [&](auto K) { cvk::heun_step_all<decltype(K)::value>(MP, x, p_cov, delta); });
+  return CURVIS_OK;
+}
+
+int curvis_walk_ray(const curvis_metric *metric, double x[4], double p_cov[4], double delta, int64_t step_scale, int32_t integrator,
+                    uint32_t max_iterations, double max_radius, uint32_t *steps, int32_t *code) {
+  if (!metric || !x || !p_cov || !steps || !code || (integrator != 0 && integrator != 1)) return CURVIS_E_INVALID;
+  if (curvis_metric_validate(metric) != CURVIS_OK) return CURVIS_E_METRIC;
+  double probe;
+  if (!cvk::step_delta_of_scale(delta, (long long)step_scale, 0.0, &probe)) return CURVIS_E_INVALID;
+  if (integrator != 0 && !(delta > 0.0)) return CURVIS_E_INVALID;
+  const cvk::MetricParams MP = make_metric(*metric);
+  const bool adapt = step_scale != 0 || integrator != 0;
+  const double kappa = step_scale != 0 ? cvk::step_kappa(delta, (long long)step_scale) : 0.0;
+  *steps = max_iterations;
+  *code = CURVIS_NOT_ESCAPED;
+  if (max_iterations == 0) return CURVIS_OK;
+  with_kind(metric->kind, [&](auto K) { /* the loop of geodesic_static, with the IEEE form of the step */
+    constexpr int KIND = decltype(K)::value;
+    for (uint32_t k = 1;; ++k) {
+      const double dk = adapt ? cvk::step_delta(delta, kappa, x[1]) : delta;
+      if (integrator) cvk::heun_step_all<KIND>(MP, x, p_cov, dk);
+      else host_euler_step<KIND>(MP, x, p_cov, dk);
+      if (std::fabs(x[1]) > max_radius) {
+        *steps = k;
+        *code = x[1] > 0.0 ? CURVIS_POSITIVE_SPACE : CURVIS_NEGATIVE_SPACE;
+        break;
+      }
+      if (k >= max_iterations) break;
+    }
+  });
   return CURVIS_OK;
 }
 

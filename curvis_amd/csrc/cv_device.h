@@ -29,7 +29,7 @@
 
 namespace cvk {
 
-enum : int { METRIC_ELLIS = 0, METRIC_INTERSTELLAR = 1, METRIC_FLAT = 2 };
+enum : int { METRIC_ELLIS = 0, METRIC_INTERSTELLAR = 1, METRIC_FLAT = 2, METRIC_SCHWARZSCHILD = 3 };
 enum : int { CODE_NONE = 0, CODE_POS = 1, CODE_NEG = -1 };
 
 struct MetricParams {
@@ -39,6 +39,9 @@ struct MetricParams {
   double pim;      /* PI*m: denominator of scaled_distance (src/metrics.rs:461) */
   double inv_pim;  /* RN(1/(PI*m)) computed on the host: lets the fast step divide by the constant with the
                       three-instruction Markstein sequence (exact for a correctly rounded reciprocal) */
+  /* Schwarzschild (m = the mass M; rho and a are ignored): the two slots above hold the kind's own constants, pim = 2M (exact) and
+   * inv_pim = RN(1/(2M)), formed once on the host like the reciprocal they replace (make_metric) -- the struct, which is part of
+   * every kernel's argument block, keeps its layout */
   double two_o_pi; /* 2.0/PI (src/metrics.rs:481) */
   cv_sc_tab_t T;   /* sin/cos table the per-ray functions read: LDS copy in the hot kernels, cv_sc_table()
                       (host static / device __constant__) everywhere else */
@@ -92,11 +95,28 @@ CV_HD void metric_eval(const MetricParams &M, double l, double &r, double &r2, d
       rd = 0.0;
     }
     r2 = r * r;
+  } else if (KIND == METRIC_SCHWARZSCHILD) {
+    /* the optical metric of Schwarzschild in the tortoise coordinate (include/curvis_hip.h has the definition; the lines below are
+     * its steps in its order).  l < 0 takes the values of l = 0 -- the funnel: R constant, R' < 0 constant, so a ray that has come
+     * this far inside the photon sphere keeps falling to -max_radius; -0 gives y = -1 like +0, a NaN stays a NaN */
+    const double lc = l < 0.0 ? 0.0 : l;
+    const double y = CV_FMA(lc, M.inv_pim, -1.0); /* l / 2M - 1 */
+    const double u = cv_tortoise_u(y, M.LT);      /* r / 2M - 1 */
+    const double w = 1.0 + u;
+    const double sq = CV_SQRT(u * w);
+    r = cv_div_nr((M.pim * w) * w, sq);           /* 2M (1 + u)^2 / sqrt(u (1 + u)) */
+    rd = cv_div_nr(2.0 * u - 1.0, 2.0 * sq);      /* (2u - 1) / (2 sqrt(u (1 + u))) */
+    r2 = r * r;
   } else {
     r = l;
     r2 = l * l;
     rd = 1.0;
   }
+}
+/* u = r / 2M - 1 of the Schwarzschild kind at radial coordinate l, by the lines above (the host accessor curvis_schwarzschild_u) */
+CV_HD double schwarzschild_u(const MetricParams &M, double l) {
+  const double lc = l < 0.0 ? 0.0 : l;
+  return cv_tortoise_u(CV_FMA(lc, M.inv_pim, -1.0), M.LT);
 }
 
 /* r(l) only (photon construction) */
@@ -366,6 +386,9 @@ CV_HD bool metric_fast_ok(int kind, const MetricParams &M, double max_radius) {
          /* x = 2(|l| - a)/(pi m) stays finite and far below overflow for every |l| <= max_radius (interstellar_eval_x_ge2
           * takes -1/x of it without range handling) */
          2.0 * max_radius * M.inv_pim < 0x1p200;
+  /* Schwarzschild: 2^-90 <= M < 2^88 gives y = l / 2M - 1 < 2^180 for |l| < 2^90 -- every operand of the solver and of the two
+   * quotients is a normal number far from the limits -- and 3 sqrt(3) M <= R < max(7.4 M, |l|) < 2^91 */
+  if (kind == METRIC_SCHWARZSCHILD) ok = ok && hi_word_in(M.m, CV_HI_2POW(-90), CV_HI_2POW(88));
   return ok;
 }
 

@@ -854,4 +854,37 @@ CV_HD double cv_log_ge2_t(double x, cv_log_tab_t T) {
 
 CV_HD double cv_log(double x) { return cv_log_t(x, cv_log_table()); }
 
+/* ------------------------------------------------------------------------- */
+/* u + log u = y  (the Schwarzschild metric's tortoise coordinate)            */
+/* ------------------------------------------------------------------------- */
+
+/* The solution u > 0 of u + log u = y for y >= -1 (u >= 0.2785), as include/curvis_hip.h defines it: a closed-form guess and
+ * CV_TORTOISE_STEPS Newton steps on g(u) = u + log u - y in the correction form, every operation individually rounded:
+ *   guess   y <  2:  t = y - 1,  u = 1 + t (1/2 + t (1/16 - t/192))       the cubic Taylor polynomial of u(y) around y = 1 (u = 1),
+ *                                                                        evaluated as fma(t, fma(t, fma(t, -1/192, 1/16), 1/2), 1)
+ *           y >= 2:  L = log y,  u = (y - L) + L / y                     the first terms of the asymptotic series
+ *   step    u <- u + (u ((y - u) - log u)) / (1 + u)
+ * The relative error of the guess is below 2^-4 on either side of y = 2 (4.7 % at y = -1, 6 % at y = 2); a Newton step takes a
+ * relative error e to e^2 / (2 (1 + u)), so four steps end below 2^-80 before rounding and the last one leaves the rounding of its own
+ * residual: (y - u) is exact once u has converged (Sterbenz) and log u carries half an ulp, which the factor u / (1 + u) scales to
+ * about an ulp of u.  The number of steps is fixed: no data-dependent iteration, no state carried from one call to the next -- one value
+ * per argument, the same on x86 and on gfx950 (log is cv_log_t, the quotients are cv_div_nr's correctly rounded ones).  A NaN y
+ * gives a NaN; arguments below -1 are not met (the caller clamps l at 0: the funnel). */
+#define CV_TORTOISE_STEPS 4
+CV_HD double cv_tortoise_u(double y, cv_log_tab_t T) {
+  double u;
+  if (y < 2.0) {
+    const double t = y - 1.0;
+    u = CV_FMA(t, CV_FMA(t, CV_FMA(t, -1.0 / 192.0, 0.0625), 0.5), 1.0);
+  } else {
+    const double L = cv_log_t(y, T);
+    u = (y - L) + cv_div_nr(L, y);
+  }
+  for (int k = 0; k < CV_TORTOISE_STEPS; ++k) {
+    const double res = (y - u) - cv_log_t(u, T);
+    u = u + cv_div_nr(u * res, 1.0 + u);
+  }
+  return u;
+}
+
 #endif /* CURVIS_CV_MATH_H */

@@ -906,6 +906,7 @@ int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *r
   const auto t_begin = std::chrono::steady_clock::now();
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
+  if ((rc = schwarzschild_camera_check(ctx, metric, cams, n_frames))) return rc;
   const uint32_t W = cams[0].res_x, H = cams[0].res_y;
   if (W == 0 || H == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
   /* compute_uniform_range's `alpha_nums - 1` underflows for 0 (a panic in the reference's default build).  1 and 2 are NOT refused:
@@ -980,6 +981,7 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   /* option "supersample" = N > 1: the camera of the N times finer grid, averaged into res_x x res_y by the kernel's epilogue */
   DirectParamsAdapt P;
   CallShape shape;
+  if ((rc = schwarzschild_camera_check(ctx, metric, cam, 1))) return rc;
   if ((rc = prepare_call_shape(ctx, cam, 1, delta, "frame too large", shape))) return rc;
   P.kappa = shape.kappa;
   const uint32_t ss = shape.ss, filter = shape.filter;

@@ -131,10 +131,11 @@ Args parse_args(int argc, char **argv) {
     else pos.push_back(s);
   }
   if (a.sub == "image" || a.sub == "video") {
-    if (pos.size() < 2) die("error: the following required arguments were not provided:\n  <IMAGE FILE 1>\n  <IMAGE FILE 2>", 2);
+    /* one image alone is a complete command under a Schwarzschild metric file (load_common: the -l background is then black) */
+    if (pos.size() < 2 && (pos.empty() || a.metric_toml.empty())) die("error: the following required arguments were not provided:\n  <IMAGE FILE 1>\n  <IMAGE FILE 2>", 2);
     if (pos.size() > 3) die("error: unexpected argument '" + pos[3] + "' found", 2);
     a.bg1 = pos[0];
-    a.bg2 = pos[1];
+    if (pos.size() >= 2) a.bg2 = pos[1];
     if (pos.size() == 3) a.out = pos[2];
     if (a.sub == "image" && !a.video_toml.empty()) die("error: unexpected argument '-v' found", 2);
     if (a.sub == "video" && !a.image_toml.empty()) die("error: unexpected argument '-i' found", 2);
@@ -189,13 +190,25 @@ struct Common {
   std::string out;
 };
 
-void load_common(const Args &a, Common &c, const char *what) {
+void load_common(const Args &a_in, Common &c, const char *what) {
   std::string err;
   auto need = [&](const std::string &f, const char *label) {
     if (!path_exists(f)) die(std::string("Error with ") + label + ": File \"" + f + "\" not found.");
   };
+  Args a = a_in;
   need(a.bg1, "background image 1");
-  need(a.bg2, "background image 2");
+  /* under a Schwarzschild metric (a metric file with `mass`) the second background is "what is painted on the horizon" and may be left
+   * out -- `curvis image <IMAGE FILE 1> [<OUTPUT FOLDER>] -m <mass file>` -- for an opaque black 1 x 1 image */
+  bool hole = false; /* a look ahead only: errors of the metric file are reported below, in the order they always were */
+  if (!a.metric_toml.empty() && path_exists(a.metric_toml)) {
+    curvis_metric peek{};
+    std::string ignored;
+    hole = metric_from_toml(a.metric_toml, peek, ignored) && peek.kind == CURVIS_METRIC_SCHWARZSCHILD;
+  }
+  if (hole && a.out.empty() && !a.bg2.empty() && is_dir(a.bg2)) a.out = a.bg2, a.bg2.clear();
+  if (a.bg2.empty() && !hole) die("error: the following required arguments were not provided:\n  <IMAGE FILE 2>", 2);
+  const bool black_horizon = a.bg2.empty();
+  if (!black_horizon) need(a.bg2, "background image 2");
   if (a.out.empty()) {
     char cwd[4096];
     if (!::getcwd(cwd, sizeof cwd)) die("Error with output folder: Could not get current working directory.");
@@ -239,7 +252,15 @@ void load_common(const Args &a, Common &c, const char *what) {
     std::thread &t;
     ~JoinEarly() { if (t.joinable()) t.join(); }
   } join_early{early_init};
-  std::thread second([&] { ok2 = jpegio::load_image(a.bg2, c.sky2, err2); });
+  std::thread second([&] {
+    if (black_horizon) {
+      c.sky2.w = c.sky2.h = 1;
+      c.sky2.rgba = {0, 0, 0, 255};
+      ok2 = true;
+    } else {
+      ok2 = jpegio::load_image(a.bg2, c.sky2, err2);
+    }
+  });
   const bool ok1 = jpegio::load_image(a.bg1, c.sky1, err);
   second.join();
   /* die() is std::exit(): it does not unwind, so JoinEarly would never run, and exit()'s handlers / the static destructors of

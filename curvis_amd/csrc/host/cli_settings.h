@@ -239,7 +239,8 @@ bool from_toml(const std::string &file, SimulationSettings &s, std::string &err)
          get_f64(t, "sampling_convergence_threshold_1", s.sampling_convergence_threshold_1, err) &&
          get_f64(t, "sampling_convergence_threshold_2", s.sampling_convergence_threshold_2, err);
 }
-/* metric file: tried as Interstellar (m, a, rho) first, then Ellis (rho) -- src/cli.rs:233-261 */
+/* metric file: tried as Interstellar (m, a, rho) first, then Ellis (rho) -- src/cli.rs:233-261 --, then, a form the reference does not
+ * have, Schwarzschild (mass): a file with `mass` and no `rho`.  Every file the first two forms read keeps its meaning. */
 bool metric_from_toml(const std::string &file, curvis_metric &m, std::string &err) {
   TomlTable t;
   if (!load_table(file, t, err)) {
@@ -259,6 +260,13 @@ bool metric_from_toml(const std::string &file, curvis_metric &m, std::string &er
     m.kind = CURVIS_METRIC_ELLIS;
     m.rho = rho;
     m.m = m.a = 0.0;
+    return true;
+  }
+  double mass;
+  if (get_f64(t, "mass", mass, e)) {
+    m.kind = CURVIS_METRIC_SCHWARZSCHILD;
+    m.m = mass;
+    m.rho = m.a = 0.0;
     return true;
   }
   err = "Could not read the metric configuration file.";

@@ -493,7 +493,7 @@ struct DirectParamsAdapt : DirectParams { /* the ADAPT instantiations' argument:
 
 /* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
 template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter", PROJ: option "projection", ADAPT: options "step_scale" (1) and "integrator" (2) */
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KIND == cvk::METRIC_INTERSTELLAR ? 4 : 6)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kind_has_log(KIND) ? 4 : 6)))
 void direct_kernel(const std::conditional_t<FILTER == 2, WithSkyMip<std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>>,
                                             std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>> P) {
   [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */

@@ -64,9 +64,13 @@ struct ShadeParams {
 /* Per-workgroup LDS copy of the sin/cos table (4 KiB; 8 KiB in its 256-row form): the Euler loop evaluates
  * sincos once per step per lane with a data-dependent index; two ds_read_b128 from LDS instead of divergent
  * __constant__ loads. */
+/* the kinds whose step evaluates a logarithm: Interstellar (with an arc tangent) and Schwarzschild (the tortoise solver, cv_math.h
+ * cv_tortoise_u: four to five of them per metric evaluation).  They keep the log table in LDS and are compiled for the register
+ * budget of five waves per SIMD (four in the direct kernel) */
+constexpr bool kind_has_log(int kind) { return kind == cvk::METRIC_INTERSTELLAR || kind == cvk::METRIC_SCHWARZSCHILD; }
 template <int KIND>
 struct alignas(16) MathTablesLds {
-  static constexpr unsigned LOG_ROWS = (KIND == cvk::METRIC_INTERSTELLAR) ? (unsigned)CV_LOG_TABLE_N : 2u;
+  static constexpr unsigned LOG_ROWS = kind_has_log(KIND) ? (unsigned)CV_LOG_TABLE_N : 2u;
   static constexpr unsigned ATAN_ROWS = (KIND == cvk::METRIC_INTERSTELLAR) ? (unsigned)CV_ATAN_TABLE_N : 1u;
   /* Order and alignment are chosen for the address arithmetic of the lookups: the 24-byte log rows sit at offset
    * 0, so ds_read2_b64 (whose offset field is short) and ds_read_b64 share one address register; the 32- and
@@ -86,6 +90,8 @@ struct alignas(16) MathTablesLds {
 static_assert(sizeof(MathTablesLds<cvk::METRIC_INTERSTELLAR>) * 5 <= 160 * 1024,
               "five workgroups of the Interstellar kernels (5 waves per SIMD) must fit the CU's 160 KiB of LDS");
 static_assert(sizeof(MathTablesLds<cvk::METRIC_ELLIS>) * 8 <= 160 * 1024, "the Ellis / flat kernels run at up to 8 workgroups per CU");
+static_assert(sizeof(MathTablesLds<cvk::METRIC_SCHWARZSCHILD>) * 5 <= 160 * 1024,
+              "five workgroups of the Schwarzschild kernels (12 KiB log + 8 KiB sin/cos: 5 waves per SIMD) must fit the CU's 160 KiB of LDS");
 
 /* copy the elementary-function tables of cv_math.h into LDS and point the metric at them */
 template <int KIND>
@@ -94,7 +100,13 @@ __device__ __forceinline__ void load_math_tables(MathTablesLds<KIND> &L, cvk::Me
   double *dst = &L.sc[0][0];
   for (unsigned i = threadIdx.x; i < (MathTablesLds<KIND>::WIDE_SC ? 1024u : 512u); i += blockDim.x) dst[i] = src[i & 511u];
   M.T = L.sc;
-  if (KIND == cvk::METRIC_INTERSTELLAR) {
+  if (KIND == cvk::METRIC_SCHWARZSCHILD) { /* the log table alone; the arc tangent is not evaluated */
+    const double *lsrc = &cv_log_table_dev[0][0];
+    double *ldst = &L.lg[0][0];
+    for (unsigned i = threadIdx.x; i < 3u * CV_LOG_TABLE_N; i += blockDim.x) ldst[i] = lsrc[i];
+    M.LT = L.lg;
+    M.AT = cv_atan_table();
+  } else if (KIND == cvk::METRIC_INTERSTELLAR) {
     const double *lsrc = &cv_log_table_dev[0][0];
     double *ldst = &L.lg[0][0];
     for (unsigned i = threadIdx.x; i < 3u * CV_LOG_TABLE_N; i += blockDim.x) ldst[i] = lsrc[i];
@@ -257,7 +269,7 @@ template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0,
   ADAPT: 1 option "step_scale" != 0: every step takes cv_device.h step_delta(P.delta, P.kappa, l) instead of P.delta (the fused kernels and
   the debug dump's staged PHI kernel, fast step only); 2 option "integrator" = 1: a step is cv_device.h ray_step_heun with that delta_k
   (kappa = +0 while "step_scale" is off: step_delta then returns P.delta for every l) */
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((KIND == cvk::METRIC_INTERSTELLAR ? 5 : 7) - (ADAPT == 2 ? 1 : 0))))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kind_has_log(KIND) ? 5 : 7) - (ADAPT == 2 ? 1 : 0))))
 void geodesic_static(const IntegrateArgsF<ADAPT, FILTER> P) { /* the Heun step holds the saved state across two stages, four register pairs more:
   at 7 (5) waves the loop would spill them, so the ADAPT = 2 kernels ask for one wave less */
   static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");

@@ -76,7 +76,7 @@ struct curvis_ctx {
                                        once, there is no dispatch phase, and the static kernel is as good) */
   uint32_t last_relay_launches = 0;
   uint64_t last_relay_parks = 0, last_relay_waiters = 0;
-  unsigned relay_resident_blocks[2][2][4][3][2] = {}; /* cached occupancy query per kernel instantiation: [projection != 0][sky_filter][log2 supersample][kind][fast] */
+  unsigned relay_resident_blocks[2][2][4][3][2] = {}; /* cached occupancy query per kernel instantiation: [projection != 0][sky_filter][log2 supersample][kind][fast]; the kind is Ellis, Interstellar or flat: the relay kernel is not instantiated for Schwarzschild */
   int relay_resident_threads = 0;                                  /* ... valid for this workgroup size */
   int block_threads = 0; /* workgroup size of the static / relay kernels: 64, 128 or 256; 0 = automatic */
   Event ev2;
@@ -192,6 +192,7 @@ auto with_kind(int kind, F &&f) {
   switch (kind) {
     case CURVIS_METRIC_ELLIS: return f(std::integral_constant<int, cvk::METRIC_ELLIS>{});
     case CURVIS_METRIC_INTERSTELLAR: return f(std::integral_constant<int, cvk::METRIC_INTERSTELLAR>{});
+    case CURVIS_METRIC_SCHWARZSCHILD: return f(std::integral_constant<int, cvk::METRIC_SCHWARZSCHILD>{});
     default: return f(std::integral_constant<int, cvk::METRIC_FLAT>{});
   }
 }
@@ -306,6 +307,15 @@ int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_f
   return CURVIS_OK;
 }
 
+/* The Schwarzschild kind in a render call (all three renderers): the coordinate l > 0 is the whole exterior, l <= 0 is the funnel that
+ * swallows captured rays (include/curvis_hip.h) -- no place for a camera. */
+int schwarzschild_camera_check(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames) {
+  if (metric->kind != CURVIS_METRIC_SCHWARZSCHILD) return CURVIS_OK;
+  for (uint32_t f = 0; f < n_frames; ++f)
+    if (!(cams[f].pos[1] > 0.0)) return fail(ctx, CURVIS_E_INVALID, "Schwarzschild metric: the camera's radial coordinate l must be greater than 0 (l <= 0 is the capture funnel)");
+  return CURVIS_OK;
+}
+
 /* ---- overlapped download of the frames (option "async_download" = 1) -------------------------------------------------
  * The reference's render_image returns an owned host image (src/systems.rs:314-329), so a host that calls one render per
  * frame pays the PCIe copy after every kernel: +0.25 ms on a 10.2 ms 1080p frame (bench.py: value_with_download, -2.4 %).
@@ -408,6 +418,10 @@ cvk::MetricParams make_metric(const curvis_metric &m) {
   M.pim = CV_PI * m.m;
   M.inv_pim = 1.0 / M.pim;
   M.two_o_pi = 2.0 / CV_PI;
+  if (m.kind == CURVIS_METRIC_SCHWARZSCHILD) { /* the kind's own constants in the same slots (cv_device.h MetricParams) */
+    M.pim = 2.0 * m.m;
+    M.inv_pim = 1.0 / M.pim;
+  }
   M.T = cv_sc_table(); /* host tables; kernels substitute their own copies (LDS or __constant__) */
   M.LT = cv_log_table();
   M.AT = cv_atan_table();
@@ -523,6 +537,7 @@ unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
 /* grid = fresh workgroups + relay workgroups; see geodesic_relay */
 template <int KIND, bool FAST, int SS, int FILTER, int PROJ>
 int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
+  static_assert(KIND != cvk::METRIC_SCHWARZSCHILD, "no relay kernel of the Schwarzschild kind: relay_resident_blocks has three kinds");
   void (*const kernel)(const IntegrateParams, const RelayArgs) = geodesic_relay<KIND, FAST, SS, FILTER, PROJ>;
   const size_t bytes = sizeof(RelayQueue) + sizeof(unsigned) * kRelayRing;
   if (int rc = ctx->d_rq.reserve(ctx, bytes)) return rc;
@@ -576,7 +591,7 @@ template <int KIND, bool PHI, bool FAST, int SS, int FILTER, int PROJ, int ADAPT
 int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused, int relay) {
   static_assert(!(PHI && FILTER == 2), "the debug dump's staged kernel has no mip-mapped lookup: render_impl refuses the call");
   const IntegrateParams &P = PA; /* what every kernel but the ADAPT ones takes */
-  if constexpr (ADAPT == 0 && FILTER != 2) /* scaled steps, Heun steps and the mip-mapped lookup never take the relay kernel (choose_render_path) */
+  if constexpr (ADAPT == 0 && FILTER != 2 && KIND != cvk::METRIC_SCHWARZSCHILD) /* scaled steps, Heun steps, the mip-mapped lookup and the Schwarzschild kind never take the relay kernel (choose_render_path) */
     if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, P, relay == 2);
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const dim3 grid((unsigned)((P.total_rays + bt - 1ull) / bt));
@@ -587,19 +602,22 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused
       staged = true;
     }
   } else if constexpr (SS == 1 && FILTER == 0 && PROJ == 0) {
-    if (ctx->variant == 0) {
-      int per_cu = ctx->blocks_per_cu;
-      if (per_cu <= 0) {
-        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, geodesic_persistent<KIND, PHI, FAST>, 256, 0));
-        if (per_cu <= 0) per_cu = 1;
+    bool persistent = false;
+    if constexpr (KIND != cvk::METRIC_SCHWARZSCHILD) /* no persistent kernel of the Schwarzschild kind: render_rays refuses variant = 0 */
+      if (ctx->variant == 0) {
+        int per_cu = ctx->blocks_per_cu;
+        if (per_cu <= 0) {
+          HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, geodesic_persistent<KIND, PHI, FAST>, 256, 0));
+          if (per_cu <= 0) per_cu = 1;
+        }
+        unsigned long long blocks = (unsigned long long)per_cu * (unsigned long long)ctx->prop.multiProcessorCount;
+        const unsigned long long max_useful = (P.total_rays + 255ull) / 256ull;
+        if (blocks > max_useful) blocks = max_useful;
+        if (blocks == 0) blocks = 1;
+        hipLaunchKernelGGL((geodesic_persistent<KIND, PHI, FAST>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
+        persistent = staged = true;
       }
-      unsigned long long blocks = (unsigned long long)per_cu * (unsigned long long)ctx->prop.multiProcessorCount;
-      const unsigned long long max_useful = (P.total_rays + 255ull) / 256ull;
-      if (blocks > max_useful) blocks = max_useful;
-      if (blocks == 0) blocks = 1;
-      hipLaunchKernelGGL((geodesic_persistent<KIND, PHI, FAST>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
-      staged = true;
-    } else if (!fused) {
+    if (!persistent && !fused) {
       hipLaunchKernelGGL((geodesic_static<KIND, PHI, FAST, false>), grid, dim3(bt), 0, ctx->stream, P);
       staged = true;
     }
@@ -710,9 +728,10 @@ RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
                                                                    : 4ull * (unsigned long long)ctx->prop.multiProcessorCount;
   const size_t relay_staging = (size_t)tiles * 64u * kStoreBytesPerPixel;
   /* option "step_scale": the static kernel -- the relay segments are sized in fixed-delta steps and its hand-over pattern was tuned on
-   * fixed-delta step counts.  Option "integrator" = 1 likewise: there is no relay form of the Heun step.  Option "sky_mipmap" = 1: no relay
+   * fixed-delta step counts (and the Schwarzschild kind, for which the relay kernel is not instantiated: its captured rays run ten times the steps of
+   * the others, a pattern the hand-over was never tuned on).  Option "integrator" = 1 likewise: there is no relay form of the Heun step.  Option "sky_mipmap" = 1: no relay
    * form either (the epilogue is not where a single frame's time goes) */
-  p.relay = !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
+  p.relay = c.metric->kind != CURVIS_METRIC_SCHWARZSCHILD && !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
             relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
   p.chunk = c.n_frames;
   p.store_bytes = p.relay ? relay_staging : 0;
@@ -977,6 +996,9 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
   const auto t_begin = std::chrono::steady_clock::now();
   int rc = curvis_metric_validate(c.metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
+  if ((rc = schwarzschild_camera_check(ctx, c.metric, c.cams, c.n_frames))) return rc;
+  if (c.metric->kind == CURVIS_METRIC_SCHWARZSCHILD && ctx->variant == 0)
+    return fail(ctx, CURVIS_E_INVALID, "Schwarzschild metric: variant = 0 (the persistent kernel) is not built for this kind (set variant = -1, 1 or 2: the static kernel renders it)");
   const uint32_t H_full = c.cams[0].res_y;
   c.W = c.cams[0].res_x;
   if (c.W == 0 || H_full == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");

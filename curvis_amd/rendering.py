@@ -157,7 +157,8 @@ class ImageRenderingSystem:
         st = self.image_rendering_settings = image_rendering_settings
         self.mode = mode
         image_1 = load_image_as_spherical_image(st.path_to_background_image_1)
-        image_2 = load_image_as_spherical_image(st.path_to_background_image_2)
+        # a SchwarzschildMetric with no second background named (None or ""): RelativisticSystem paints the horizon black
+        image_2 = load_image_as_spherical_image(st.path_to_background_image_2) if st.path_to_background_image_2 else None
         camera = Camera(st.camera_position, st.camera_forward, st.camera_up, st.camera_focal_length, st.camera_diagonal,
                         st.resolution_x, st.resolution_y)
         self.relativistic_system = RelativisticSystem(metric, image_1, image_2, camera, context=context)
@@ -264,7 +265,7 @@ class VideoRenderingSystem:
         `alphas_num` and `max_iterations_sampling` separately and `sampling_convergence_threshold_1` twice (:299-307);
         so does this (threshold_2 of the settings is never read, as there)."""
         from .images import load_image_as_spherical_image
-        from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context
+        from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context, SchwarzschildMetric, black_sky
         check_supersample(supersample)  # before the context and the files are touched
         check_sky_mipmap(sky_mipmap)
         check_step_scale(step_scale)
@@ -274,7 +275,10 @@ class VideoRenderingSystem:
         st = video_rendering_settings
         context = context or default_context()
         context.set_sky(0, load_image_as_spherical_image(st.filepath_to_background_image_1))
-        context.set_sky(1, load_image_as_spherical_image(st.filepath_to_background_image_2))
+        if st.filepath_to_background_image_2 or not isinstance(metric, SchwarzschildMetric):
+            context.set_sky(1, load_image_as_spherical_image(st.filepath_to_background_image_2))
+        else:  # a SchwarzschildMetric with no second background named: the horizon is painted black
+            context.set_sky(1, black_sky())
         self = cls(metric, context, Interpolator.from_file(str(st.filepath_to_camera_path)), st.frame_rate,
                    (st.resolution_x, st.resolution_y), st.camera_diagonal, st.camera_focal_length, st.escape_radius,
                    st.max_iterations_propagation, st.ray_integration_step, rank=rank, world_size=world_size, batch=batch,

@@ -180,14 +180,33 @@ class InterstellarMetricSettings(_Settings):
         return InterstellarMetric(self.m, self.a, self.rho)
 
 
+class SchwarzschildMetricSettings(_Settings):
+    """not in the reference: a metric file with the key `mass` (and no `rho`) is a Schwarzschild black hole"""
+    FIELDS = (("mass", float, 1.0),)
+
+    def validate(self):
+        if not self.mass > 0.0:
+            raise SettingsError("The mass parameter mass must be larger than zero.")
+
+    def metric(self):
+        from .systems import SchwarzschildMetric
+        return SchwarzschildMetric(self.mass)
+
+
 def metric_settings_from_toml_file(path):
-    """src/cli.rs:233-261: a metric file is tried as Interstellar settings first, then as Ellis settings"""
+    """src/cli.rs:233-261: a metric file is tried as Interstellar settings first, then as Ellis settings; then (not in the
+    reference) as Schwarzschild settings, so every file the first two forms read keeps its meaning"""
     try:
         return InterstellarMetricSettings.from_toml_file(path)
     except SettingsError as first:
         try:
             return EllisMetricSettings.from_toml_file(path)
         except SettingsError:
+            try:
+                if "rho" not in _load_toml(path):
+                    return SchwarzschildMetricSettings.from_toml_file(path)
+            except SettingsError:
+                pass
             # src/cli.rs:255-259: neither parse succeeded -> the reference's one message, not the first parser's
             raise SettingsError("Could not read the metric configuration file.") from first
 

@@ -153,6 +153,58 @@ class FlatSphericalMetric(DiagonalSphericalMetric):
         return Metric(_abi.METRIC_FLAT, 0, 0.0, 0.0, 0.0)
 
 
+class SchwarzschildMetric(DiagonalSphericalMetric):
+    """A Schwarzschild black hole of mass `mass` (not in the reference; include/curvis_hip.h, CURVIS_METRIC_SCHWARZSCHILD): the
+    optical metric in the tortoise coordinate l = r + 2M log(r/2M - 1), whose r(l) is r / sqrt(1 - 2M/r).  Null geodesics and local
+    angles are Schwarzschild's; proper time and redshift are not represented.  A ray is captured when it escapes to -l: the
+    background of the -l side is what is painted on the horizon (the rendering systems set a black one when none is named)."""
+
+    def __init__(self, mass):
+        if not mass > 0.0:
+            raise ValueError("The mass parameter for Schwarzschild Metrics must be positive.")
+        self.mass = float(mass)
+
+    def _c(self):
+        return Metric(_abi.METRIC_SCHWARZSCHILD, 0, 0.0, self.mass, 0.0)
+
+    def l_of_radius(self, r):
+        """tortoise coordinate of the areal radius r > 2M (a host float: not part of the bit-exact contract)"""
+        import math
+        two_m = 2.0 * self.mass
+        if not r > two_m:
+            raise ValueError("the areal radius must be greater than 2M")
+        return r + two_m * math.log(r / two_m - 1.0)
+
+    def radius_of_l(self, l):
+        """areal radius at the tortoise coordinate l (a host float: Newton on u + log u = l/2M - 1 from the library's own u for
+        l >= 0, and from exp(y) below, where the kernels' funnel has no solution to give)"""
+        import math
+        two_m = 2.0 * self.mass
+        y = l / two_m - 1.0
+        if y < -30.0:
+            return two_m * (1.0 + math.exp(y))
+        u = math.exp(y) if y < 0.0 else max(y - math.log(max(y, 1.0)), 0.5)
+        for _ in range(60):
+            nu = u + u * (y - u - math.log(u)) / (1.0 + u)
+            if nu == u:
+                break
+            u = nu if nu > 0.0 else 0.5 * u
+        return two_m * (1.0 + u)
+
+    def u(self, l):
+        """u = r/2M - 1 at l exactly as the kernels compute it (curvis_schwarzschild_u)"""
+        m = self._c()
+        out = C.c_double(0.0)
+        check(lib().curvis_schwarzschild_u(C.byref(m), float(l), C.byref(out)))
+        return out.value
+
+
+def black_sky():
+    """the 1 x 1 opaque black background the rendering systems paint on the horizon of a SchwarzschildMetric when the caller names
+    none"""
+    return SphericalImage(np.array([[[0, 0, 0, 255]]], dtype=np.uint8))
+
+
 def _vec(v, n):
     a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(n))
     return a
@@ -865,7 +917,8 @@ class RelativisticSystem:
     def __init__(self, metric, background_positive, background_negative, camera, context=None):
         self.metric = metric
         self.background_positive = background_positive
-        self.background_negative = background_negative
+        # a SchwarzschildMetric without a -l background: the horizon is painted black
+        self.background_negative = black_sky() if background_negative is None and isinstance(metric, SchwarzschildMetric) else background_negative
         self.camera = camera
         self.context = context if context is not None else default_context()
         self.last_stats = None

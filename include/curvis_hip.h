@@ -46,7 +46,48 @@ enum {
 };
 
 /* enum Metric (src/metrics.rs:575-578) + FlatSphericalMetric (src/metrics.rs:492-505) */
-enum { CURVIS_METRIC_ELLIS = 0, CURVIS_METRIC_INTERSTELLAR = 1, CURVIS_METRIC_FLAT = 2 };
+enum { CURVIS_METRIC_ELLIS = 0, CURVIS_METRIC_INTERSTELLAR = 1, CURVIS_METRIC_FLAT = 2, CURVIS_METRIC_SCHWARZSCHILD = 3 };
+
+/* CURVIS_METRIC_SCHWARZSCHILD: a Schwarzschild black hole of mass M (field `m`; `rho` and `a` are ignored; valid iff m > 0), a kind the
+ * reference does not have.  It fits the reference's trait DiagonalSphericalMetric (g00 = -1, g11 = 1, one function r(l)) through the OPTICAL
+ * metric: null geodesics and the angles a static observer measures are conformally invariant, and Schwarzschild's metric divided by
+ * (1 - 2M/r), written in the tortoise coordinate, has exactly the trait's form,
+ *     l    = r + 2M log(r/2M - 1)           r the areal radius, r > 2M
+ *     R(l) = r / sqrt(1 - 2M/r)             what the trait calls r(l)
+ * R has its minimum 3 sqrt(3) M at the photon sphere (r = 3M, l = 1.614 M), R -> |l| for l -> +inf, and R grows without bound for
+ * l -> -inf, the horizon.  In this picture the hole is a wormhole whose far side is the horizon: a ray is captured exactly when it
+ * escapes to -l, so the escape test, the which-side code and the counters (n_neg = captured rays) are the ones every kind has, and the
+ * sky set for -l is "what is painted on the horizon" -- set an opaque black one and the shadow appears.  What is represented: the null
+ * geodesics and the local angles of Schwarzschild, for a camera that is a static observer at areal radius r(l_camera).  What is not:
+ * proper time and redshift (curvis_metric_functions and curvis_metric_tensor return the optical metric, whose g00 is -1).
+ *
+ * Definition of R, R^2 and R' at l -- an explicit sequence of individually rounded FP64 operations, one text for host and device
+ * (cv_device.h metric_eval, cv_math.h cv_tortoise_u), a pure function of l: no iteration count that depends on the data, nothing
+ * carried over from the previous step.  inv = RN(1 / (2M)) and 2M (exact) are formed once per call on the host.
+ *   0. lc = l < 0 ? 0 : l                                (the funnel, below; -0 and +0 give the same y; a NaN stays)
+ *   1. y  = fma(lc, inv, -1)                             l/2M - 1; with u = r/2M - 1 > 0 the tortoise relation reads u + log u = y
+ *   2. guess:  y < 2:  t = y - 1,  u = fma(t, fma(t, fma(t, -1/192, 1/16), 1/2), 1)       (Taylor polynomial of u(y) at y = 1)
+ *              else:   L = log y,  u = (y - L) + L / y                                     (asymptotic series)
+ *   3. four times:  u = u + (u * ((y - u) - log u)) / (1 + u)                              (Newton on u + log u - y, correction form)
+ *   4. w = 1 + u,  q = sqrt(u * w)
+ *   5. R  = ((2M * w) * w) / q                           = 2M (1 + u)^(3/2) / sqrt(u)
+ *      R' = (2 * u - 1) / (2 * q)                        = dR/dl = (2u - 1) / (2 sqrt(u (1 + u)))
+ *      R^2 = R * R
+ * log is cv_math.h's cv_log_t (full domain); every quotient and the root are the correctly rounded ones (IEEE `/` and sqrt on the
+ * host, their Markstein forms on the device -- never a bare hardware seed).  Measured against mpmath at 40 digits
+ * (profiles/schwarzschild_accuracy.txt): R within 3.3 ulp; R' passes through zero at the photon sphere, where the error of u (about an ulp)
+ * is up to 6 400 ulp of the small R'.  Bit-for-bit agreement of host and device is
+ * asserted for 2^-90 <= M < 2^88 and |l| < 2^90 (the fast step's guard); outside, a quotient of the device may lose its last bit.
+ *
+ * The funnel.  For l < 0 (y < -1, u < 0.2785, r < 2.557 M: well inside the photon sphere) the three functions are DEFINED as their
+ * values at l = 0: R is constant and R' < 0 is constant, so dp_l = b^2 R' / R^3 <= 0 and a ray that enters l < 0 moving inward keeps
+ * p_l < 0 and reaches -max_radius.  No ray that escapes to +l ever goes below the photon sphere, so the region is never seen and the
+ * solver never needs exp or arguments below y = -1.  The funnel is a capture device, not physics.  A render call whose camera has
+ * l <= 0 fails with CURVIS_E_INVALID under this kind.
+ *
+ * Kernels: the static kernel (fused, with every option, and the debug dump's staged form), both step flavours, the samplers, the
+ * direct renderer and trajectories.  There is no relay and no persistent kernel of the kind: the automatic choice and "variant" = 2 take
+ * the static kernel, and "variant" = 0 is refused with CURVIS_E_INVALID. */
 
 /* EllisMetric { rho } (src/metrics.rs:399-401), InterstellarMetric { m, a, rho } (:431-435). */
 typedef struct curvis_metric {
@@ -160,12 +201,15 @@ int curvis_camera_init(curvis_camera *out, const double pos[4], const double for
 /* Orientation::new: rotation matrix, its inverse and the orthogonalised up (any may be NULL). */
 int curvis_orientation_init(const double forward[3], const double up[3], double rot[9], double inv_rot[9],
                             double up_out[3]);
-/* EllisMetric::new / InterstellarMetric::new parameter checks (src/metrics.rs:407-459). */
+/* EllisMetric::new / InterstellarMetric::new parameter checks (src/metrics.rs:407-459); Schwarzschild: m > 0 (false for a NaN). */
 int curvis_metric_validate(const curvis_metric *m);
 /* The three required methods of trait DiagonalSphericalMetric (src/metrics.rs:40-48: r, r_squared, r_derivative;
  * Ellis :417-421, Interstellar :467-485, flat :501-505) at radial coordinate l, evaluated on the host with the same
  * arithmetic (cv_math.h) the kernels use -- what every ray of a render is integrated with.  Any output may be NULL. */
 int curvis_metric_functions(const curvis_metric *m, double l, double *r, double *r_squared, double *r_derivative);
+/* CURVIS_METRIC_SCHWARZSCHILD only (any other kind: CURVIS_E_INVALID): u = r/2M - 1 at radial coordinate l as steps 0-3 of the kind's
+ * definition above compute it -- the number R and R' are formed from (R' has the sign of 2u - 1 exactly). */
+int curvis_schwarzschild_u(const curvis_metric *m, double l, double *u);
 /* The diagonal of the metric tensor at `position` = (t, l, theta, phi): covariant g_ii = (-1, 1, r^2(l),
  * r^2(l) sin^2(theta)) (src/metrics.rs:49-68; sin().powi(2) is s * s) and contravariant g^ii = g_ii.powi(-1) = 1 / g_ii
  * (:84-93) -- what to_covariant / to_contravariant (:163-219) multiply a vector's components by.  Host-side, same
@@ -206,6 +250,13 @@ int curvis_update_relativistic_object(const curvis_metric *metric, double x[4], 
  * `out`, and S != 0 with !(delta > 0).  Fed into curvis_update_relativistic_object it walks a ray the way the kernels do. */
 #define CURVIS_STEP_SCALE_MAX (1u << 20)
 int curvis_step_delta(double delta, int64_t step_scale, double l, double *out);
+/* A whole ray on the host: from (x, p_cov), in place, the loop the render kernels run -- step size from curvis_step_delta's text (S = step_scale),
+ * one step of curvis_update_relativistic_object (integrator = 0) or curvis_heun_step (1), the escape test |l| > max_radius, at most
+ * max_iterations steps -- with the IEEE form of the step.  *steps and *code (CURVIS_POSITIVE_SPACE, CURVIS_NEGATIVE_SPACE, CURVIS_NOT_ESCAPED)
+ * are what curvis_render_brute_debug records for the ray; x[0] is its time.  One call instead of one per step for host-side references.
+ * CURVIS_E_INVALID for a null pointer, an integrator other than 0 or 1, S outside [0, 2^20], and S != 0 or integrator = 1 with !(delta > 0). */
+int curvis_walk_ray(const curvis_metric *metric, double x[4], double p_cov[4], double delta, int64_t step_scale, int32_t integrator,
+                    uint32_t max_iterations, double max_radius, uint32_t *steps, int32_t *code);
 /* Option "integrator" = 1 (defined with the options below) for ONE step: a Heun step of (x, p_cov) in place, on the host, all eight
  * components, with the IEEE form of the Euler step (cv_device.h ray_step_heun, the text the kernels' loops call; the fast step
  * returns the same bits).  x[0] is averaged like the other coordinates; p_cov[0] and p_cov[3] keep their bits.  With `delta` taken
