@@ -280,6 +280,36 @@ int curvis_ctx_set_sky_orientation(curvis_ctx *ctx, int which, const double forw
   return CURVIS_OK;
 }
 
+int curvis_ctx_set_disc(curvis_ctx *ctx, const uint8_t *rgba, uint32_t w, uint32_t h, double l_inner, double l_outer) {
+  if (!ctx) return CURVIS_E_INVALID;
+  if (!rgba) { /* remove the disc: every call launches the kernels it launched before one was set */
+    ctx->disc_set = false;
+    return CURVIS_OK;
+  }
+  if (w == 0 || h == 0) return fail(ctx, CURVIS_E_INVALID, "disc: empty texture");
+  if (!std::isfinite(l_inner) || !std::isfinite(l_outer)) return fail(ctx, CURVIS_E_INVALID, "disc: l_inner and l_outer must be finite");
+  if (!(l_inner < l_outer)) return fail(ctx, CURVIS_E_INVALID, "disc: l_inner must be less than l_outer");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); /* nothing in flight reads the texture that reserve may free */
+  ctx->disc_set = false;
+  if (int rc = ctx->d_disc.reserve(ctx, (size_t)w * h)) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_disc, rgba, (size_t)w * h * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->disc_w = w, ctx->disc_h = h;
+  ctx->disc_l_in = l_inner, ctx->disc_l_out = l_outer;
+  ctx->disc_set = true;
+  return CURVIS_OK;
+}
+
+int curvis_disc_crossing(double c_prev, double c_cur, double s_cur, double l_prev, double l_cur, double phi_prev, double phi_cur,
+                         double l_inner, double l_outer, uint32_t w, uint32_t h, int32_t *hit, uint32_t *tx, uint32_t *ty) {
+  if (!hit || !tx || !ty || w == 0 || h == 0) return CURVIS_E_INVALID;
+  unsigned x = 0, y = 0;
+  *hit = cvk::disc_crossing(c_prev, c_cur, s_cur, l_prev, l_cur, phi_prev, phi_cur, l_inner, l_outer, w, h, &x, &y) ? 1 : 0;
+  *tx = x, *ty = y;
+  return CURVIS_OK;
+}
+
 /* what RCCL itself has to say about a failure: the result's text, the communicator's last error, an asynchronous error */
 static std::string rccl_detail(ncclComm_t comm, ncclResult_t rc) {
   std::string m = ncclGetErrorString(rc);
@@ -758,12 +788,21 @@ int curvis_render_brute_batch(curvis_ctx *ctx, const curvis_metric *metric, cons
   return render_impl(ctx, metric, cameras, n_frames, max_iterations, max_radius, delta, rgb_out, nullptr, stats);
 }
 
+/* the efficient and the direct renderer reduce every ray to an equatorial orbit: no theta, no plane to cross */
+static int refuse_disc(curvis_ctx *ctx, const char *renderer) {
+  if (!ctx) return CURVIS_OK; /* the call itself says so */
+  ctx->last_frame_disc.clear();
+  if (!ctx->disc_set) return CURVIS_OK;
+  return fail(ctx, CURVIS_E_INVALID, std::string("a disc is set: ") + renderer + " reduces every ray to an equatorial orbit and cannot see it -- the brute renderer does (or remove the disc: curvis_ctx_set_disc with rgba = NULL)");
+}
+
 int curvis_render_efficient(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *camera,
                             uint32_t max_iterations_propagation, double max_radius, double delta, uint32_t alpha_nums,
                             uint32_t max_iterations_sampling, double sampling_convergence_threshold_1,
                             double sampling_convergence_threshold_2, uint8_t *rgb_out, curvis_stats *stats) {
   const EfficientCall call = {metric, camera, 1, max_iterations_propagation, max_radius, delta, alpha_nums, max_iterations_sampling,
                               sampling_convergence_threshold_1, sampling_convergence_threshold_2};
+  if (int rc = refuse_disc(ctx, "the efficient renderer")) return rc;
   return render_efficient_impl(ctx, call, rgb_out, stats);
 }
 
@@ -774,6 +813,7 @@ int curvis_render_efficient_batch(curvis_ctx *ctx, const curvis_metric *metric, 
                                   uint8_t *rgb_out, curvis_stats *stats) {
   const EfficientCall call = {metric, cameras, n_frames, max_iterations_propagation, max_radius, delta, alpha_nums, max_iterations_sampling,
                               sampling_convergence_threshold_1, sampling_convergence_threshold_2};
+  if (int rc = refuse_disc(ctx, "the efficient renderer")) return rc;
   return render_efficient_impl(ctx, call, rgb_out, stats);
 }
 
@@ -783,11 +823,13 @@ int curvis_ctx_prefetch_efficient(curvis_ctx *ctx, const curvis_metric *metric, 
                                   double sampling_convergence_threshold_2) {
   const EfficientCall call = {metric, cameras, n_frames, max_iterations_propagation, max_radius, delta, alpha_nums, max_iterations_sampling,
                               sampling_convergence_threshold_1, sampling_convergence_threshold_2};
+  if (ctx && ctx->disc_set) return fail(ctx, CURVIS_E_INVALID, "a disc is set: the efficient renderer, whose sampler this call runs ahead of time, cannot see it");
   return prefetch_efficient_impl(ctx, call);
 }
 
 int curvis_render_direct(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *camera, uint32_t max_iterations,
                          double max_radius, double delta, uint8_t *rgb_out, curvis_stats *stats) {
+  if (int rc = refuse_disc(ctx, "the direct renderer")) return rc;
   return render_direct_impl(ctx, metric, camera, max_iterations, max_radius, delta, rgb_out, stats);
 }
 
@@ -800,6 +842,12 @@ int curvis_ctx_sampling_info(const curvis_ctx *ctx, uint32_t frame, curvis_sampl
 int curvis_ctx_frame_stats(const curvis_ctx *ctx, uint32_t frame, curvis_stats *stats) {
   if (!ctx || !stats || frame >= ctx->last_frame_stats.size()) return CURVIS_E_INVALID;
   *stats = ctx->last_frame_stats[frame];
+  return CURVIS_OK;
+}
+
+int curvis_ctx_frame_disc_hits(const curvis_ctx *ctx, uint32_t frame, uint64_t *n_disc) {
+  if (!ctx || !n_disc || frame >= ctx->last_frame_stats.size()) return CURVIS_E_INVALID;
+  *n_disc = frame < ctx->last_frame_disc.size() ? ctx->last_frame_disc[frame] : 0;
   return CURVIS_OK;
 }
 

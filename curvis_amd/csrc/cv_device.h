@@ -30,7 +30,7 @@
 namespace cvk {
 
 enum : int { METRIC_ELLIS = 0, METRIC_INTERSTELLAR = 1, METRIC_FLAT = 2, METRIC_SCHWARZSCHILD = 3 };
-enum : int { CODE_NONE = 0, CODE_POS = 1, CODE_NEG = -1 };
+enum : int { CODE_NONE = 0, CODE_POS = 1, CODE_NEG = -1, CODE_DISC = 2 /* ended on the disc (the DISC kernels) */ };
 
 struct MetricParams {
   double rho;      /* throat radius */
@@ -164,6 +164,17 @@ CV_HD void ray_step(const MetricParams &M, Ray &q, double delta) {
     cv_sincos_tw(q.th, M.T, &s, &c);
   else
     cv_sincos_t(q.th, M.T, &s, &c);
+  ray_step_core<KIND, PHI>(M, q, delta, s, c);
+}
+/* the same step under a probe that is handed the (sin, cos) of theta before the state moves (ray_step_fast's PROBE has the contract) */
+template <int KIND, bool PHI, bool WIDE_T, class PROBE>
+CV_HD void ray_step_probed(const MetricParams &M, Ray &q, double delta, const PROBE &probe) {
+  double s, c;
+  if (WIDE_T)
+    cv_sincos_tw(q.th, M.T, &s, &c);
+  else
+    cv_sincos_t(q.th, M.T, &s, &c);
+  probe.sincos(s, c);
   ray_step_core<KIND, PHI>(M, q, delta, s, c);
 }
 
@@ -403,6 +414,16 @@ struct NoProbe {
 #endif
   inline void rec(int, double, double, double) const {}
 };
+/* The other thing a probe can be handed: the (sin, cos) of theta that the step evaluates anyway, from whichever branch forms them,
+ * BEFORE the step touches the state -- `probe.sincos(s, c)`.  The disc test of the per-pixel kernels lives there (kernels_geodesic.h
+ * DiscProbe: the signs of two consecutive cosines say whether the ray crossed the equatorial plane, disc_crossing below).  Only a probe
+ * type that says so is asked -- a specialisation of probe_takes_sincos -- so the instantiations under every other probe are compiled
+ * from the text they had. */
+template <class PROBE>
+struct probe_takes_sincos {
+  static constexpr bool value = false;
+};
+
 /* one Newton step on an approximate reciprocal.  For y within an ulp of 1/d the result is RN(1/d) unless d's
  * significand is all ones (Markstein); with y = RN(1/d) div_with_recip is correctly rounded, not just almost always.
  * Only the CV_CERTIFIED_DIV build (an A/B measurement, tools/gpu_ab.py) calls it inside the step. */
@@ -433,6 +454,7 @@ CV_HD void ray_step_fast(const MetricParams &M, Ray &q, double delta, bool lane_
   } else {
     s_ok = cv_sincos_guarded(q.th, M.T, WIDE_T ? 1 : 0, &s, &c);
   }
+  if constexpr (probe_takes_sincos<PROBE>::value) probe.sincos(s, c);
   /* guard (branch-free, one compare each): sin(theta) and l non-zero, not NaN and far from the underflow
    * limit.  Upper bounds are implied: |sin| <= 1, and a step is only executed for a ray that has not
    * escaped, |l| <= max_radius < 2^90 (metric_fast_ok; an infinite l has escaped, a NaN fails the compare).
@@ -575,12 +597,14 @@ CV_HD void ray_step_fast(const MetricParams &M, Ray &q, double delta, bool lane_
  * the Euler loops call.  With the same instantiation the compiler's inliner, which weighs a function by all of its callers, compiled
  * the Interstellar direct, escape-angle and sampler kernels of the EULER step with two instructions in another order. */
 struct HeunStage : NoProbe {};
-template <int KIND, bool PHI, bool FAST, bool WIDE_T = false, bool EQ = false>
-CV_HD void ray_step_heun(const MetricParams &M, Ray &q, double delta, bool lane_ok) {
+/* STAGE1: the probe of the first stage (FAST only) -- the disc test is handed that stage's (sin, cos), those of the state the step starts
+ * from; stage states are never looked at */
+template <int KIND, bool PHI, bool FAST, bool WIDE_T = false, bool EQ = false, class STAGE1 = HeunStage>
+CV_HD void ray_step_heun(const MetricParams &M, Ray &q, double delta, bool lane_ok, const STAGE1 &stage1 = STAGE1()) {
   const double l0 = q.l, th0 = q.th, p10 = q.p1, p20 = q.p2;
   [[maybe_unused]] const double ph0 = PHI ? q.ph : 0.0;
   if (FAST) {
-    ray_step_fast<KIND, PHI, WIDE_T, EQ, HeunStage>(M, q, delta, lane_ok);
+    ray_step_fast<KIND, PHI, WIDE_T, EQ, STAGE1>(M, q, delta, lane_ok, stage1);
     ray_step_fast<KIND, PHI, WIDE_T, EQ, HeunStage>(M, q, delta, lane_ok && CV_FABS(q.l) < 0x1p90);
   } else {
     ray_step<KIND, PHI, WIDE_T>(M, q, delta);
@@ -760,6 +784,31 @@ CV_HD double rem_euclid_pos(double a, double b) {
     r = fmod(a, b);
   }
   return (r < 0.0) ? r + b : r;
+}
+
+/* ---- the accretion disc (include/curvis_hip.h has the definition; the lines below are its steps 1-7 in its order, every operation
+ * individually rounded, no fma of their own).  Between two consecutive states of a ray -- (c_prev, l_prev, ph_prev) of y_{k-1}, (s_cur, c_cur,
+ * l_cur, ph_cur) of y_k, s and c being the sincos evaluation of theta the step from that state performs anyway -- did the ray cross the
+ * plane theta = pi/2 (mod pi) at a radial coordinate inside [l_in, l_out], and at which texel of a w x h texture?  One text for host and
+ * device: the per-pixel kernels call it inside their rarely taken crossing branch, curvis_disc_crossing is its host accessor.  The
+ * quotients are the correctly rounded ones: t and the column's through cv_div_nr (operands a cosine apart resp. an angle below 2 pi
+ * over a constant: far inside the range where its Markstein form is exact), the row's through the operator, whose operands are the
+ * caller's bounds and may sit anywhere in the exponent range.  A NaN anywhere fails the range compare. */
+CV_HD bool disc_crossing(double c_prev, double c_cur, double s_cur, double l_prev, double l_cur, double ph_prev, double ph_cur, double l_in,
+                         double l_out, unsigned w, unsigned h, unsigned *tx, unsigned *ty) {
+  if ((c_prev < 0.0) == (c_cur < 0.0)) return false;                    /* 1 */
+  const double t = cv_div_nr(c_prev, c_prev - c_cur);                   /* 2 */
+  const double dl = l_cur - l_prev, dph = ph_cur - ph_prev;
+  const double l_hit = l_prev + t * dl;                                 /* 3 */
+  double ph_hit = ph_prev + t * dph;
+  if (!(l_in <= l_hit && l_hit <= l_out)) return false;                 /* 4 */
+  if (s_cur < 0.0) ph_hit = ph_hit + CV_PI;                             /* 5 */
+  const double TWO_PI = 2.0 * CV_PI;
+  const unsigned x = rust_as_u32(cv_div_nr(rem_euclid_pos(ph_hit, TWO_PI), TWO_PI) * (double)w); /* 6 */
+  const unsigned y = rust_as_u32(((l_hit - l_in) / (l_out - l_in)) * (double)h);                 /* 7 */
+  *tx = x < w - 1u ? x : w - 1u;
+  *ty = y < h - 1u ? y : h - 1u;
+  return true;
 }
 
 struct SkyParams {

@@ -22,7 +22,17 @@ struct Args {
   int projection = 0; /* pixel -> direction (library option "projection"): 0 perspective, 1 equirectangular, 2 fisheye */
   long long step_scale = 0; /* --step-scale L0 as library option "step_scale" = 256 L0: 0 off, else the Euler step grows as |l| / L0 outside L0 */
   int integrator = 0; /* --integrator euler|heun (library option "integrator"): 0 forward Euler, 1 Heun's method, two Euler steps averaged */
+  std::string disc; /* --disc FILE --disc-inner L --disc-outer L: an accretion disc (curvis_ctx_set_disc) textured with the image FILE between
+                       the radial coordinates L; all three or none, and --mode brute, the one renderer that sees it */
+  std::string disc_inner_s, disc_outer_s;
+  double disc_inner = 0.0, disc_outer = 0.0;
 };
+/* the disc of the run (Args::disc, decoded by load_common) for make_ctx_bare: every context gets it */
+struct DiscOfRun {
+  bool set = false;
+  pngio::Image img;
+  double l_inner = 0.0, l_outer = 0.0;
+} g_disc;
 int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
 int g_sky_filter = 0;  /* Args::sky_filter, likewise */
 int g_sky_mipmap = 0;  /* Args::sky_mipmap, likewise */
@@ -44,7 +54,8 @@ void usage() {
       "              [--sky-broadcast rccl|upload] [--writers T] [--resume] [--png-level -1..9] [--gpu-png auto|on|off]\n"
       "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n"
       "              [--projection perspective|equirectangular|fisheye] [--step-scale L0]\n"
-      "              [--integrator euler|heun] [--sky-mipmap on|off]\n");
+      "              [--integrator euler|heun] [--sky-mipmap on|off]\n"
+      "              [--disc <IMAGE FILE> --disc-inner L --disc-outer L]  (an accretion disc; needs --mode brute)\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -126,6 +137,9 @@ Args parse_args(int argc, char **argv) {
       if (val != "euler" && val != "heun") die("error: --integrator must be euler or heun", 2);
       a.integrator = g_integrator = val == "heun" ? 1 : 0;
     }
+    else if (key == "--disc") take(a.disc);
+    else if (key == "--disc-inner") take(a.disc_inner_s);
+    else if (key == "--disc-outer") take(a.disc_outer_s);
     else if (key == "-h" || key == "--help") { usage(); std::exit(0); }
     else if (!s.empty() && s[0] == '-') die("error: unexpected argument '" + s + "' found", 2);
     else pos.push_back(s);
@@ -141,6 +155,19 @@ Args parse_args(int argc, char **argv) {
     if (a.sub == "video" && !a.image_toml.empty()) die("error: unexpected argument '-i' found", 2);
   }
   if (a.mode != "efficient" && a.mode != "brute" && a.mode != "direct") die("error: --mode must be efficient, brute or direct", 2);
+  if (!a.disc.empty() || !a.disc_inner_s.empty() || !a.disc_outer_s.empty()) {
+    if (a.disc.empty() || a.disc_inner_s.empty() || a.disc_outer_s.empty())
+      die("error: --disc, --disc-inner and --disc-outer are given together, or none of them", 2);
+    auto number = [](const std::string &v, double &out) {
+      char *end = nullptr;
+      out = std::strtod(v.c_str(), &end);
+      return !v.empty() && *end == '\0' && std::isfinite(out);
+    };
+    if (!number(a.disc_inner_s, a.disc_inner) || !number(a.disc_outer_s, a.disc_outer) || !(a.disc_inner < a.disc_outer))
+      die("error: --disc-inner and --disc-outer must be finite numbers, the inner one less than the outer", 2);
+    /* no silent change of mode: the efficient and the direct renderer reduce every ray to an equatorial orbit and cannot see a disc */
+    if (a.mode != "brute") die("error: --disc needs --mode brute (the per-pixel renderer is the one that sees a disc); this run is --mode " + a.mode, 2);
+  }
   if (a.sky_broadcast != "rccl" && a.sky_broadcast != "upload") die("error: --sky-broadcast must be rccl or upload", 2);
   if (a.gpu_png != "auto" && a.gpu_png != "on" && a.gpu_png != "off") die("error: --gpu-png must be auto, on or off", 2);
   if (a.devices < 1) a.devices = 1;
@@ -269,6 +296,13 @@ void load_common(const Args &a_in, Common &c, const char *what) {
   if ((!ok1 || !ok2) && early_init.joinable()) early_init.join();
   if (!ok1) die(std::string("Error in rendering ") + what + ": background image 1: " + err);
   if (!ok2) die(std::string("Error in rendering ") + what + ": background image 2: " + err2);
+  if (!a.disc.empty()) {
+    if (early_init.joinable()) early_init.join(); /* as above: die() must not race hipInit */
+    need(a.disc, "disc image");
+    if (!jpegio::load_image(a.disc, g_disc.img, err)) die(std::string("Error in rendering ") + what + ": disc image: " + err);
+    g_disc.l_inner = a.disc_inner, g_disc.l_outer = a.disc_outer;
+    g_disc.set = true;
+  }
 }
 
 void check(int rc, curvis_ctx *ctx, const char *what) {
@@ -299,6 +333,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
   if (g_projection != 0) check(curvis_ctx_set_option(ctx, "projection", g_projection), ctx, what);
   if (g_step_scale != 0) check(curvis_ctx_set_option(ctx, "step_scale", g_step_scale), ctx, what);
   if (g_integrator != 0) check(curvis_ctx_set_option(ctx, "integrator", g_integrator), ctx, what);
+  if (g_disc.set) check(curvis_ctx_set_disc(ctx, g_disc.img.rgba.data(), g_disc.img.w, g_disc.img.h, g_disc.l_inner, g_disc.l_outer), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {

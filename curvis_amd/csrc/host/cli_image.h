@@ -31,6 +31,7 @@ int image_main(const Args &a) {
   std::vector<uint8_t> rgb((size_t)cam.res_x * cam.res_y * 3);
   curvis_stats st;
   std::memset(&st, 0, sizeof st);
+  unsigned long long n_disc = 0; /* rays that ended on the disc (--disc) */
   if (a.mode == "brute" && a.devices > 1) {
     /* --mode brute --devices N: the rows of the ONE frame are split over N GPUs (rays are independent,
      * src/systems.rs:316-326); one host thread + one context per GPU, the bands land in place in `rgb` */
@@ -63,10 +64,14 @@ int image_main(const Args &a) {
       st.n_none += sts[(size_t)r].n_none;
       st.n_oob += sts[(size_t)r].n_oob;
       st.kernel_ms = std::max(st.kernel_ms, sts[(size_t)r].kernel_ms);
+      uint64_t band_disc = 0;
+      if (g_disc.set && sts[(size_t)r].rays != 0 && curvis_ctx_frame_disc_hits(ctxs[(size_t)r], 0, &band_disc) == CURVIS_OK) n_disc += band_disc;
       if (r > 0) curvis_ctx_destroy(ctxs[(size_t)r]);
     }
   } else {
     check(render_frames(ctx, a, c, &cam, 1, c.sim.sampling_convergence_threshold_2, rgb.data(), &st), ctx, "image");
+    uint64_t frame_disc = 0;
+    if (g_disc.set && curvis_ctx_frame_disc_hits(ctx, 0, &frame_disc) == CURVIS_OK) n_disc = frame_disc;
   }
   clk.mark("render");
   /* PathBuf::join(image_name).with_extension("png") (src/rendering.rs:108): an existing extension is REPLACED */
@@ -77,9 +82,11 @@ int image_main(const Args &a) {
   if (!a.stats.empty()) {
     FILE *f = std::fopen(a.stats.c_str(), "w");
     if (f) {
-      std::fprintf(f, "{\"frame\": 0, \"mode\": \"%s\", \"supersample\": %d, \"sky_filter\": \"%s\", \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f}\n",
+      /* with a disc set the line carries n_disc: rays = n_pos + n_neg + n_none + n_disc */
+      const std::string disc_field = g_disc.set ? ", \"n_disc\": " + std::to_string(n_disc) : std::string();
+      std::fprintf(f, "{\"frame\": 0, \"mode\": \"%s\", \"supersample\": %d, \"sky_filter\": \"%s\", \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu%s, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f}\n",
                    a.mode.c_str(), a.supersample, a.sky_filter ? "bilinear" : "nearest", (unsigned long long)st.rays, (unsigned long long)st.steps, (unsigned long long)st.n_pos,
-                   (unsigned long long)st.n_neg, (unsigned long long)st.n_none, (unsigned long long)st.n_oob, st.kernel_ms,
+                   (unsigned long long)st.n_neg, (unsigned long long)st.n_none, (unsigned long long)st.n_oob, disc_field.c_str(), st.kernel_ms,
                    st.kernel_ms > 0.0 ? (double)st.steps / st.kernel_ms / 1e3 : 0.0);
       std::fclose(f);
     }

@@ -471,10 +471,12 @@ int video_main(const Args &a_in) {
           fs = g_direct_frame_stats[j];
         else
           (void)curvis_ctx_frame_stats(ctx, (uint32_t)j, &fs);
+        uint64_t fs_disc = 0; /* --disc: the frame's rays that ended on the disc */
+        if (g_disc.set) (void)curvis_ctx_frame_disc_hits(ctx, (uint32_t)j, &fs_disc);
         const double batch_ms = st.kernel_ms;
         const uint32_t frame_crc = streams && have_crc ? zcrc[j] : 0u;
         const bool frame_has_crc = streams && have_crc;
-        auto job = [&, k, frame, f_len, streams, batch_buf, copy, fs, nb, rank, batch_ms, batch_call_ms, frame_crc, frame_has_crc] {
+        auto job = [&, k, frame, f_len, streams, batch_buf, copy, fs, fs_disc, nb, rank, batch_ms, batch_call_ms, frame_crc, frame_has_crc] {
           const std::string file = tmp + "/frame_" + std::to_string(k) + ".png";
           const std::string part = file + ".part"; /* written under another name, then renamed: --resume never sees half a file */
           std::string e;
@@ -510,11 +512,12 @@ int video_main(const Args &a_in) {
             pr.first->frames += pr.second->frames;
           }
           std::printf("Rendering frame %zu/%zu...\n", k + 1, times.size());
+          const std::string disc_field = g_disc.set ? ", \"n_disc\": " + std::to_string((unsigned long long)fs_disc) : std::string();
           if (stats_f)
-            std::fprintf(stats_f, "{\"frame\": %zu, \"time\": %.17g, \"device\": %d, \"mode\": \"%s\", \"supersample\": %d, \"sky_filter\": \"%s\", \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f, \"batch_frames\": %zu, \"batch_kernel_ms\": %.4f, \"batch_call_ms\": %.4f}\n",
+            std::fprintf(stats_f, "{\"frame\": %zu, \"time\": %.17g, \"device\": %d, \"mode\": \"%s\", \"supersample\": %d, \"sky_filter\": \"%s\", \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu%s, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f, \"batch_frames\": %zu, \"batch_kernel_ms\": %.4f, \"batch_call_ms\": %.4f}\n",
                          k, times[k], device_of(rank), a.mode.c_str(), a.supersample, a.sky_filter ? "bilinear" : "nearest", (unsigned long long)fs.rays, (unsigned long long)fs.steps,
                          (unsigned long long)fs.n_pos, (unsigned long long)fs.n_neg, (unsigned long long)fs.n_none,
-                         (unsigned long long)fs.n_oob, fs.kernel_ms, fs.kernel_ms > 0.0 ? (double)fs.steps / fs.kernel_ms / 1e3 : 0.0, nb,
+                         (unsigned long long)fs.n_oob, disc_field.c_str(), fs.kernel_ms, fs.kernel_ms > 0.0 ? (double)fs.steps / fs.kernel_ms / 1e3 : 0.0, nb,
                          batch_ms, batch_call_ms);
         };
         if (hold_back)

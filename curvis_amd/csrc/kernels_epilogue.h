@@ -15,7 +15,7 @@ namespace {
  * 0.40 ms), so a frame's counters are spread over 64 lines in launches of a few frames and over 8 in larger
  * batches.  The host sums the replicas of a frame, and the frames for the totals of the call. */
 enum { CNT_NEXT = 0 };
-enum { FC_STEPS = 0, FC_RAYS, FC_POS, FC_NEG, FC_NONE, FC_OOB, FC_N };
+enum { FC_STEPS = 0, FC_RAYS, FC_POS, FC_NEG, FC_NONE, FC_OOB, FC_DISC /* rays that ended on the disc: the DISC kernels alone add to it */, FC_N };
 enum { CNT_STRIDE = 16 };
 struct FrameCounters {
   unsigned long long *base; /* device: CNT_STRIDE * (1 + n_frames * slots) words */
@@ -109,6 +109,15 @@ __device__ __forceinline__ void sky_lookup(const cvk::SkyParams &S, double d0, d
   }
 }
 
+/* The seventh counter, FC_DISC: the rays of a wave's tile that ended on the disc (include/curvis_hip.h), added to the counters of the
+ * tile's frame.  A function of its own, called by the DISC kernels behind flush_frame_counts, which stays the text it was: `frame` is
+ * the wave-uniform frame of the tile (frame_of_tile), lanes with !valid contribute nothing, one lane issues the one atomic. */
+__device__ __forceinline__ void flush_disc_count(const FrameCounters &C, unsigned frame, bool valid, unsigned disc) {
+  if (!valid) disc = 0u;
+  for (int off = 32; off > 0; off >>= 1) disc += __shfl_xor(disc, off);
+  if ((threadIdx.x & 63u) == 0u && disc) atomicAdd(&frame_counter_line(C, frame)[FC_DISC], (unsigned long long)disc);
+}
+
 /* the three colour bytes of a texel (Rgba, red in the low byte) -> one RGB8 pixel */
 __device__ __forceinline__ void store_rgb8(unsigned char *dst, unsigned texel) {
   dst[0] = (unsigned char)(texel & 0xFF);
@@ -172,6 +181,16 @@ struct SkyMipArgs {
 template <typename Base>
 struct WithSkyMip : Base {
   SkyMipArgs mip;
+};
+/* ---- the accretion disc (include/curvis_hip.h): its texture and bounds, appended to the argument of the DISC kernels the same way */
+struct DiscArgs {
+  const unsigned *texels; /* w x h RGBA8, w along azimuth, h along l */
+  unsigned w, h;
+  double l_in, l_out;
+};
+template <typename Base>
+struct WithDisc : Base {
+  DiscArgs disc;
 };
 /* Called by EVERY lane of a wave that holds one 8x8 tile of rays whose origin is even in both absolute ray coordinates: `which` is 0
  * (no sky: capped, or outside the frame), 1 (+l sky) or 2 (-l sky), (Xc, Yc) the lane's indices on its own sky.  The lanes exchange the

@@ -49,6 +49,9 @@ using IntegrateArgs = std::conditional_t<ADAPT != 0, IntegrateParamsAdapt, Integ
 /* FILTER = 2 (option "sky_mipmap"): either of the two with the skies' level tables appended (kernels_epilogue.h WithSkyMip) */
 template <int ADAPT, int FILTER>
 using IntegrateArgsF = std::conditional_t<FILTER == 2, WithSkyMip<IntegrateArgs<ADAPT>>, IntegrateArgs<ADAPT>>;
+/* DISC = 1 (a disc is set, include/curvis_hip.h): any of the four with the disc appended (kernels_epilogue.h WithDisc) */
+template <int ADAPT, int FILTER, int DISC>
+using IntegrateArgsD = std::conditional_t<DISC != 0, WithDisc<IntegrateArgsF<ADAPT, FILTER>>, IntegrateArgsF<ADAPT, FILTER>>;
 
 struct ShadeParams {
   cvk::MetricParams metric;
@@ -167,6 +170,52 @@ __device__ __forceinline__ void heun_step(const cvk::MetricParams &M, double del
   cvk::ray_step_heun<KIND, PHI, FAST, MathTablesLds<KIND>::WIDE_SC, EQ>(M, q, delta, lane_ok);
 }
 
+/* The disc test of the DISC kernels (include/curvis_hip.h, the disc's paragraph), as the probe of the step from y_k: it is handed
+ * (s_k, c_k) while q is still y_k, so the loop carries l, phi and cos(theta) of y_{k-1} and nothing else.  The hot path pays two sign
+ * compares, a ballot and a scalar branch; cv_device.h disc_crossing (three divisions), the gather and the alpha test sit behind the
+ * branch, taken in the few iterations in which some lane of the wave changes hemisphere.  A lane that ends here gets its texel (alpha
+ * >= 128, so non-zero); the step it is inside of runs to its end and is discarded by the loop. */
+struct DiscProbe {
+  const DiscArgs &D;
+  const cvk::Ray &q;
+  double &l_prev, &ph_prev, &c_prev;
+  unsigned &texel;
+  bool first; /* k = 0 (wave-uniform): there is no previous state */
+  __device__ __forceinline__ void rec(int, double, double, double) const {}
+  __device__ __forceinline__ void sincos(double s, double c) const {
+    const bool crossed = !first & ((c_prev < 0.0) != (c < 0.0));
+    if (__builtin_amdgcn_ballot_w64(crossed)) {
+      if (crossed) {
+        unsigned tx, ty;
+        if (cvk::disc_crossing(c_prev, c, s, l_prev, q.l, ph_prev, q.ph, D.l_in, D.l_out, D.w, D.h, &tx, &ty)) {
+          const unsigned t = D.texels[(size_t)ty * D.w + tx];
+          if ((t >> 24) >= 128u) texel = t;
+        }
+      }
+    }
+    l_prev = q.l, ph_prev = q.ph, c_prev = c;
+  }
+};
+}  // namespace
+template <>
+struct cvk::probe_takes_sincos<DiscProbe> {
+  static constexpr bool value = true;
+};
+namespace {
+/* a step of a DISC kernel: the call's step flavour with phi integrated, under the probe (with Heun, the first stage's) */
+template <int KIND, bool FAST, bool HEUN>
+__device__ __forceinline__ void disc_step(const cvk::MetricParams &M, double delta, cvk::Ray &q, bool lane_ok, const DiscProbe &probe) {
+  constexpr bool W = MathTablesLds<KIND>::WIDE_SC;
+  if constexpr (HEUN) {
+    static_assert(FAST, "the Heun step exists for the fast step only");
+    cvk::ray_step_heun<KIND, true, true, W, false, DiscProbe>(M, q, delta, lane_ok, probe);
+  } else if constexpr (FAST) {
+    cvk::ray_step_fast<KIND, true, W, false, DiscProbe>(M, q, delta, lane_ok, probe);
+  } else {
+    cvk::ray_step_probed<KIND, true, W, DiscProbe>(M, q, delta, probe);
+  }
+}
+
 /* final photon -> tangent direction -> nearest sky texel (rows R9-R10 of SURVEY.md 8a); FILTER: the bilinear blend instead */
 template <int KIND, int FILTER = 0>
 __device__ __forceinline__ unsigned shade_ray(const cvk::MetricParams &M, const cvk::SkyParams *sky, const cvk::Ray &q,
@@ -262,20 +311,37 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
  * free in occupancy and removes ~200 MB of HBM traffic and one launch per frame.
  * SS: supersampling factor (1: one ray per output pixel; 2, 4, 8: P is in units of the fine grid and the epilogue averages,
  * kernels_epilogue.h resolve_store; FUSED only). */
-template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter" (FUSED only),
+/* Waves per SIMD that the DISC form of a kernel gives up against its plain form, from the compiler's resource report (profiles/disc_asm_diff.txt):
+ * the loop carries l, phi and cos(theta) of the previous state, phi itself and the texel, nine VGPRs more.  The Ellis Euler forms
+ * still fit 7 waves (71-72 VGPRs) -- all but the strict step under the mip-mapped epilogue, which spilled 16 bytes there in a trial build (73 VGPRs at 6) -- and every
+ * Schwarzschild form its budget (79-80 of 96, Heun 94 of 128); the Interstellar Euler forms would spill at 5 waves (they take up to 104 at 4), the
+ * Ellis Heun forms at 6 (87 at 5) and the flat ones at 7 (up to 73 at 6); the Interstellar Heun forms fit the 4 waves they have (115-117 of 128).
+ * With these, no DISC kernel uses scratch. */
+constexpr int disc_wave_cost(int kind, int adapt, bool fast, int filter) {
+  if (kind == cvk::METRIC_SCHWARZSCHILD) return 0;
+  if (kind == cvk::METRIC_INTERSTELLAR) return adapt == 2 ? 0 : 1;
+  if (kind == cvk::METRIC_ELLIS) return (adapt == 2 || (!fast && filter == 2)) ? 1 : 0; /* the strict step under the mip epilogue spilled 16 bytes at 7 */
+  return 1;
+}
+template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0, int DISC = 0> /* FILTER: option "sky_filter" (FUSED only),
   2 with option "sky_mipmap" on top: the epilogue finds every ray's (Xc, Yc), the wave exchanges them inside its 2 x 2 quads and each lane
   blends two levels of the sky's mip chain (kernels_epilogue.h sky_mip_shade);
   PROJ: 0 the reference's perspective mapping, 1 option "projection" != 0 (P.projection says which; FUSED only);
   ADAPT: 1 option "step_scale" != 0: every step takes cv_device.h step_delta(P.delta, P.kappa, l) instead of P.delta (the fused kernels and
   the debug dump's staged PHI kernel, fast step only); 2 option "integrator" = 1: a step is cv_device.h ray_step_heun with that delta_k
-  (kappa = +0 while "step_scale" is off: step_delta then returns P.delta for every l) */
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kind_has_log(KIND) ? 5 : 7) - (ADAPT == 2 ? 1 : 0))))
-void geodesic_static(const IntegrateArgsF<ADAPT, FILTER> P) { /* the Heun step holds the saved state across two stages, four register pairs more:
+  (kappa = +0 while "step_scale" is off: step_delta then returns P.delta for every l);
+  DISC: 1 while the context holds a disc (include/curvis_hip.h; FUSED, and the one fused form that integrates phi): the loop keeps l, phi
+  and cos(theta) of the previous state, tests the sign of the cosine each step hands out -- a ballot and a scalar branch -- and, inside the
+  branch, calls cv_device.h disc_crossing, gathers the texel and ends the ray where it is opaque; four register pairs and a dword more
+  than the parent's loop, which costs some of the DISC kernels a wave (disc_wave_cost) */
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kind_has_log(KIND) ? 5 : 7) - (ADAPT == 2 ? 1 : 0) - (DISC ? disc_wave_cost(KIND, ADAPT, FAST, FILTER) : 0))))
+void geodesic_static(const IntegrateArgsD<ADAPT, FILTER, DISC> P) { /* the Heun step holds the saved state across two stages, four register pairs more:
   at 7 (5) waves the loop would spill them, so the ADAPT = 2 kernels ask for one wave less */
-  static_assert(SS == 1 || (FUSED && !PHI), "supersampling resolves in the fused epilogue");
-  static_assert(FILTER == 0 || (FUSED && !PHI), "the filtered lookup exists in the fused epilogues only");
-  static_assert(PROJ == 0 || (FUSED && !PHI), "the projections exist in the fused kernels only");
-  static_assert(ADAPT == 0 || (FAST && (FUSED != PHI)), "scaled steps exist for the fast step, in the fused kernels and the debug dump's");
+  static_assert(DISC == 0 || (FUSED && PHI), "the disc exists in the fused kernels, which then integrate phi");
+  static_assert(SS == 1 || (FUSED && (!PHI || DISC)), "supersampling resolves in the fused epilogue");
+  static_assert(FILTER == 0 || (FUSED && (!PHI || DISC)), "the filtered lookup exists in the fused epilogues only");
+  static_assert(PROJ == 0 || (FUSED && (!PHI || DISC)), "the projections exist in the fused kernels only");
+  static_assert(ADAPT == 0 || (FAST && ((FUSED != PHI) || DISC)), "scaled steps exist for the fast step, in the fused kernels and the debug dump's");
   __shared__ MathTablesLds<KIND> s_tab;
   cvk::MetricParams M = P.metric;
   load_math_tables<KIND>(s_tab, M);
@@ -302,7 +368,37 @@ void geodesic_static(const IntegrateArgsF<ADAPT, FILTER> P) { /* the Heun step h
    * ballot mask so that the compiler keeps the block inside the loop instead of sinking it behind the exit,
    * which would cost a counter copy to a VGPR in every iteration).  Lanes still inside when the counter
    * reaches max_iterations are NotEscaped (code stays CODE_NONE). */
-  if (active) {
+  [[maybe_unused]] unsigned on_disc = 0u;    /* DISC: 1 for a ray that ended on the disc, for the frame's n_disc */
+  [[maybe_unused]] unsigned disc_texel = 0u; /* DISC: the texel the ray ended on; its alpha is >= 128, so non-zero says "ended on the disc" */
+  if constexpr (DISC != 0) {
+    /* The disc loop: the parent's, with the plane test inside the step (DiscProbe) at the point where the step from y_k has its
+     * (s_k, c_k) and the state is still y_k.  A lane that ended on the disc leaves as an escaping lane does, through the same ballot; its
+     * count is k, the steps before the one it was found in, and nothing of that step's result is read again -- its colour is the texel. */
+    if (active) {
+      const unsigned lane = threadIdx.x & 63u;
+      unsigned k = 0;
+      steps = P.max_iter;
+      double l_prev = 0.0, ph_prev = 0.0, c_prev = 0.0;
+      for (;;) {
+        double dk = P.delta;
+        if constexpr (ADAPT != 0) dk = cvk::step_delta(P.delta, P.kappa, q.l);
+        disc_step<KIND, FAST, ADAPT == 2>(M, dk, q, lane_ok_w, DiscProbe{P.disc, q, l_prev, ph_prev, c_prev, disc_texel, k == 0u});
+        ++k;
+        const bool hit = disc_texel != 0u;
+        const bool esc = hit | ray_escaped(q.l, P.max_radius);
+        const unsigned long long em = __builtin_amdgcn_ballot_w64(esc);
+        if (em) { /* rare, as in the parent's loop */
+          unsigned kv;
+          asm volatile("v_mov_b32 %0, %1" : "=v"(kv) : "s"(k));
+          if ((em >> lane) & 1ull) steps = kv - (hit ? 1u : 0u);
+        }
+        if (esc) break;
+        if (k >= P.max_iter) break;
+      }
+      if (disc_texel != 0u) code = cvk::CODE_DISC;
+      else if (ray_escaped(q.l, P.max_radius)) code = escape_code(q.l);
+    }
+  } else if (active) {
     const unsigned lane = threadIdx.x & 63u;
     unsigned k = 0;
     steps = P.max_iter;
@@ -344,7 +440,7 @@ void geodesic_static(const IntegrateArgsF<ADAPT, FILTER> P) { /* the Heun step h
   if constexpr (FILTER == 2) {
     unsigned which = 0u, Xc = 0u, Yc = 0u; /* the lane's sky (0: none) and its indices on it, for the exchange */
     if (valid) {
-      if (code != cvk::CODE_NONE) {
+      if (code != cvk::CODE_NONE && (DISC == 0 || code != cvk::CODE_DISC)) { /* a disc ray saw no sky: which = 0 in the exchange */
         double d0, d1, d2;
         cvk::ray_direction<KIND>(M, q, d0, d1, d2);
         unsigned tx, ty;
@@ -354,17 +450,28 @@ void geodesic_static(const IntegrateArgsF<ADAPT, FILTER> P) { /* the Heun step h
       pos = (code == cvk::CODE_POS);
       neg = (code == cvk::CODE_NEG);
       none = (code == cvk::CODE_NONE);
+      if constexpr (DISC != 0) on_disc = (code == cvk::CODE_DISC);
     }
     seen = sky_mip_shade(P.mip, P.sky, which, Xc, Yc); /* the whole wave: lanes outside the frame answer "none" */
+    if constexpr (DISC != 0)
+      if (on_disc) seen = disc_texel; /* ... then takes its own colour, unfiltered */
     if constexpr (SS == 1)
       if (valid) store_rgb8(P.fb + slot * 3, seen);
   } else if (valid) {
     if (FUSED) {
       unsigned tx, ty;
-      const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
-      /* the plain store in THIS branch: the compiler does not merge a second test of `valid` behind the shading with the first */
-      if constexpr (SS == 1) store_rgb8(P.fb + slot * 3, texel);
-      else seen = texel;
+      if constexpr (DISC != 0) { /* a disc ray's colour is its texel: no direction, no lookup, no filter */
+        unsigned colour;
+        if (code == cvk::CODE_DISC) colour = disc_texel, on_disc = 1u;
+        else colour = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
+        if constexpr (SS == 1) store_rgb8(P.fb + slot * 3, colour);
+        else seen = colour;
+      } else {
+        const unsigned texel = shade_ray<KIND, FILTER>(M, P.sky, q, code, tx, ty, oob);
+        /* the plain store in THIS branch: the compiler does not merge a second test of `valid` behind the shading with the first */
+        if constexpr (SS == 1) store_rgb8(P.fb + slot * 3, texel);
+        else seen = texel;
+      }
       pos = (code == cvk::CODE_POS);
       neg = (code == cvk::CODE_NEG);
       none = (code == cvk::CODE_NONE);
@@ -377,6 +484,7 @@ void geodesic_static(const IntegrateArgsF<ADAPT, FILTER> P) { /* the Heun step h
   /* statistics of the wave's tile go to the counters of ITS frame (a tile never straddles frames); on the staged
    * path shade_kernel keeps them */
   if (FUSED) flush_frame_counts(P.counters, frame_of_tile(id2 >> 6, P.rays_per_frame), valid, steps, 1u, pos, neg, none, oob);
+  if constexpr (DISC != 0) flush_disc_count(P.counters, frame_of_tile(id2 >> 6, P.rays_per_frame), valid, on_disc);
   if (P.trace && (threadIdx.x & 63u) == 0) {
     unsigned hw_id, xcc_id;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));

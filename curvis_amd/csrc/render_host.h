@@ -23,6 +23,12 @@ struct curvis_ctx {
   /* skies */
   SkyTexture sky[2];
   double sky_inv_rot[2][9];
+  /* the accretion disc (include/curvis_hip.h): at most one, the context's own copy of its texture; the brute renderer's DISC kernels read it */
+  DeviceBuffer<unsigned> d_disc;
+  bool disc_set = false;
+  unsigned disc_w = 0, disc_h = 0;
+  double disc_l_in = 0.0, disc_l_out = 0.0;
+  std::vector<uint64_t> last_frame_disc; /* rays that ended on the disc, per frame of the last brute render (curvis_ctx_frame_disc_hits) */
   /* frame resources */
   DeviceBuffer<unsigned char> d_fb;
   size_t fb_bytes = 0;
@@ -638,11 +644,32 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused
   return CURVIS_OK;
 }
 
-/* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled, never filtered and always in perspective */
+/* A disc is set: the DISC form of the fused static kernel, its argument the plain form's with the disc appended.  Every call shape
+ * that reaches here has one (render_impl refuses the debug dump, variant = 0 and fuse_shade = 0 while a disc is set). */
+template <int KIND, bool FAST, int SS, int FILTER, int PROJ, int ADAPT>
+int launch_disc(curvis_ctx *ctx, const IntegrateParamsAdapt &PA) {
+  const unsigned bt = integrate_block_threads(ctx, KIND);
+  const dim3 grid((unsigned)((PA.total_rays + bt - 1ull) / bt));
+  IntegrateArgsD<ADAPT, FILTER, 1> PD;
+  static_cast<IntegrateArgs<ADAPT> &>(PD) = PA;
+  if constexpr (FILTER == 2) PD.mip = sky_mip_args(ctx);
+  PD.disc.texels = ctx->d_disc;
+  PD.disc.w = ctx->disc_w;
+  PD.disc.h = ctx->disc_h;
+  PD.disc.l_in = ctx->disc_l_in;
+  PD.disc.l_out = ctx->disc_l_out;
+  hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, true, SS, FILTER, PROJ, ADAPT, 1>), grid, dim3(bt), 0, ctx->stream, PD);
+  HIP_TRY(ctx, hipGetLastError());
+  return CURVIS_OK;
+}
+
+/* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled, never filtered and always in perspective
+ * -- and by the DISC kernels, which are fused and take every option */
 int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParamsAdapt &P, uint32_t ss,
                          uint32_t filter, int adapt) {
   return with_launch_shape(kind, fast, ss, filter, (uint32_t)P.projection, adapt, [&](auto S) {
     using T = decltype(S);
+    if (ctx->disc_set) return launch_disc<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>(ctx, P);
     if constexpr (T::SS == 1 && T::FILTER == 0 && T::PROJ == 0)
       if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0, 0, T::ADAPT>(ctx, P, false, 0);
     return launch_integrate<T::KIND, false, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>(ctx, P, fused, relay);
@@ -731,7 +758,8 @@ RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
    * fixed-delta step counts (and the Schwarzschild kind, for which the relay kernel is not instantiated: its captured rays run ten times the steps of
    * the others, a pattern the hand-over was never tuned on).  Option "integrator" = 1 likewise: there is no relay form of the Heun step.  Option "sky_mipmap" = 1: no relay
    * form either (the epilogue is not where a single frame's time goes) */
-  p.relay = c.metric->kind != CURVIS_METRIC_SCHWARZSCHILD && !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
+  /* a disc: the static kernel too -- there is no relay form of the DISC kernels */
+  p.relay = !ctx->disc_set && c.metric->kind != CURVIS_METRIC_SCHWARZSCHILD && !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
             relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
   p.chunk = c.n_frames;
   p.store_bytes = p.relay ? relay_staging : 0;
@@ -867,6 +895,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
     sum_frame_counters(ctx->h_counters, FC.slots, f, fc);
     for (int k = 0; k < FC_N; ++k) tot.counts[k] += fc[k];
     counts_to_stats(fc, ctx->last_frame_stats[f0 + f]);
+    ctx->last_frame_disc[f0 + f] = fc[FC_DISC];
     launch_steps += fc[FC_STEPS];
   }
   /* the frames of a launch run interleaved on the GPU: times are the launch's, shared out by executed Euler steps */
@@ -1041,6 +1070,7 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
   const cvk::MetricParams MP = make_metric(*c.metric);
   RenderTotals tot;
   ctx->last_frame_stats.assign(c.n_frames, curvis_stats{});
+  ctx->last_frame_disc.assign(c.n_frames, 0);
   for (uint32_t f0 = 0; f0 < c.n_frames; f0 += path.chunk) {
     rc = render_chunk(ctx, c, path, MP, f0, std::min(path.chunk, c.n_frames - f0), tot);
     if (rc == kRenderAgain) return render_again(ctx, c, true);
@@ -1084,6 +1114,12 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
   BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u, 0u};
+  /* a disc (include/curvis_hip.h) lives in the fused static kernel alone: the staged paths have no slot for a disc colour */
+  if (ctx && ctx->disc_set) {
+    if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "a disc is set: the debug dump shades from the ray store, which has no slot for a disc colour (remove the disc: curvis_ctx_set_disc with rgba = NULL)");
+    if (ctx->variant == 0) return fail(ctx, CURVIS_E_INVALID, "a disc is set: variant = 0 (the persistent kernel) shades from the ray store, which has no slot for a disc colour");
+    if (ctx->fuse_shade == 0) return fail(ctx, CURVIS_E_INVALID, "a disc is set: fuse_shade = 0 shades from the ray store, which has no slot for a disc colour");
+  }
   if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->sky_mipmap && !ctx->projection && !ctx->step_scale && !ctx->integrator)) return render_rays(ctx, c);
   /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under
    * the name of the projection when it is on, else of the filter when that is on, else of the supersampling when that is on.  The scaled

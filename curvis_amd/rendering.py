@@ -115,6 +115,18 @@ def render_image_sharded(context, metric, camera, max_iterations, max_radius, de
     return np.concatenate([p[1] for p in parts], axis=0), [p[0] for p in parts]
 
 
+def check_disc_mode(disc, mode):
+    """an accretion disc (curvis_amd.Disc) lives in the per-pixel renderer alone: ValueError for anything but a Disc or None, and for a
+    Disc with a mode other than "brute" -- there is no silent change of mode"""
+    from .systems import Disc
+    if disc is None:
+        return
+    if not isinstance(disc, Disc):
+        raise ValueError("disc must be a curvis_amd.Disc or None")
+    if mode != "brute":
+        raise ValueError("a disc needs mode='brute': mode=%r reduces every ray to an equatorial orbit and cannot see it" % (mode,))
+
+
 class ImageRenderingSettings:
     """ImageRenderingSettings (src/rendering.rs, fields as used by ImageRenderingSystem::new / render :33-117)."""
 
@@ -137,12 +149,14 @@ class ImageRenderingSystem:
     reference; 0 is its fixed step) lets the Euler step grow as |l| / L0 outside the distance L0 (library option "step_scale"); integrator="heun" (not in the
     reference; "euler" is its loop) integrates with Heun's method, two Euler steps averaged (library option "integrator");
     sky_mipmap=True (not in the reference; needs sky_filter="bilinear") takes the blend on a mip pyramid of the sky (library option
-    "sky_mipmap")."""
+    "sky_mipmap"); disc=Disc(...) (not in the reference) puts an accretion disc into the equatorial plane, which only mode="brute"
+    can see: any other mode raises ValueError."""
 
     def __init__(self, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-                 projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
+                 projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
         from .images import load_image_as_spherical_image
         from .systems import RelativisticSystem, check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
+        check_disc_mode(disc, mode)
         check_step_scale(step_scale)
         self.step_scale = step_scale
         check_integrator(integrator)
@@ -161,14 +175,14 @@ class ImageRenderingSystem:
         image_2 = load_image_as_spherical_image(st.path_to_background_image_2) if st.path_to_background_image_2 else None
         camera = Camera(st.camera_position, st.camera_forward, st.camera_up, st.camera_focal_length, st.camera_diagonal,
                         st.resolution_x, st.resolution_y)
-        self.relativistic_system = RelativisticSystem(metric, image_1, image_2, camera, context=context)
+        self.relativistic_system = RelativisticSystem(metric, image_1, image_2, camera, context=context, disc=disc)
 
     @classmethod
     def new(cls, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-            projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
+            projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
         """ImageRenderingSystem::new(metric, image_rendering_settings) (src/rendering.rs:33-70)"""
         return cls(metric, image_rendering_settings, context=context, mode=mode, supersample=supersample, sky_filter=sky_filter,
-                   projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap)
+                   projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap, disc=disc)
 
     def render(self):
         import os
@@ -222,13 +236,17 @@ class VideoRenderingSystem:
     the reference; 0 is its fixed step): library option "step_scale" on every frame.  integrator="heun" (not in the reference;
     "euler" is its loop): library option "integrator" on every frame, the prefetch included.  sky_mipmap=True (not in the reference;
     needs sky_filter="bilinear"): library option "sky_mipmap" on every frame -- the blend on a mip pyramid of the sky, which lowers the
-    frame-to-frame flicker of the strongly minified secondary images (measured in profiles/sky_mipmap_quality.txt)."""
+    frame-to-frame flicker of the strongly minified secondary images (measured in profiles/sky_mipmap_quality.txt).  disc=Disc(...) (not
+    in the reference): an accretion disc in the equatorial plane on every frame; it needs mode="brute" (ValueError otherwise), and the
+    per-frame statistics then carry n_disc, the rays that ended on it (rays = n_pos + n_neg + n_none + n_disc)."""
 
     def __init__(self, metric, context, interpolator, frame_rate, resolution, camera_diagonal, camera_focal_length,
                  escape_radius, max_iterations_propagation, ray_integration_step, rank=0, world_size=1, batch=8,
                  mode="efficient", sampling_initial_nums=100, sampling_convergence_threshold_1=1e-5, supersample=1,
-                 sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
+                 sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
         from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
+        check_disc_mode(disc, mode)
+        self.disc = disc
         self._step_scale = check_step_scale(step_scale)
         self.step_scale = step_scale
         self._sky_mipmap = check_sky_mipmap(sky_mipmap)
@@ -259,7 +277,7 @@ class VideoRenderingSystem:
 
     @classmethod
     def new(cls, metric, video_rendering_settings, context=None, rank=0, world_size=1, batch=8, mode="efficient", supersample=1,
-            sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False):
+            sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
         """VideoRenderingSystem::new(metric, video_rendering_settings) (src/rendering.rs:188-221): loads the two
         backgrounds into the context's HBM and the camera path into an Interpolator.  The reference passes
         `alphas_num` and `max_iterations_sampling` separately and `sampling_convergence_threshold_1` twice (:299-307);
@@ -267,6 +285,7 @@ class VideoRenderingSystem:
         from .images import load_image_as_spherical_image
         from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context, SchwarzschildMetric, black_sky
         check_supersample(supersample)  # before the context and the files are touched
+        check_disc_mode(disc, mode)
         check_sky_mipmap(sky_mipmap)
         check_step_scale(step_scale)
         check_integrator(integrator)
@@ -284,7 +303,8 @@ class VideoRenderingSystem:
                    st.max_iterations_propagation, st.ray_integration_step, rank=rank, world_size=world_size, batch=batch,
                    mode=mode, sampling_initial_nums=st.alphas_num,
                    sampling_convergence_threshold_1=st.sampling_convergence_threshold_1, supersample=supersample,
-                   sky_filter=sky_filter, projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap)
+                   sky_filter=sky_filter, projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap,
+                   disc=disc)
         self.max_iterations_sampling = int(st.max_iterations_sampling)
         self.video_rendering_settings = st
         return self
@@ -385,6 +405,11 @@ class VideoRenderingSystem:
         times = self.times_of_frames()
         mine = frames_of_rank(len(times), self.rank, self.world_size)
         out = []
+        disc = self.disc
+        # the context's disc is this system's, None included (a context shared between systems must not leak one); a context without the
+        # entry point, such as the tests' stubs, never had one to remove
+        if (disc is not None or hasattr(self.context, "set_disc")) and self.context._disc_obj is not disc:
+            self.context.set_disc(disc)
         batches = [mine[b0:b0 + self.batch] for b0 in range(0, len(mine), self.batch)]
         cams_of = lambda idx: [self.camera_at(times[k]) for k in idx]  # noqa: E731
         nxt = cams_of(batches[0]) if batches else None
@@ -403,11 +428,14 @@ class VideoRenderingSystem:
                 except CurvisError:
                     frames = list(self.context.download_frames(self.resolution[0], self.resolution[1], len(cams)))
             assert len(per) == len(idx)
+            done_before = len(out)
             for k, frame, s in zip(idx, frames, per):
                 d = dict(frame=k, time=times[k], rank=self.rank, mode=self.mode, batch_frames=len(idx),
                          rays=int(s.rays), steps=int(s.steps), n_pos=int(s.n_pos), n_neg=int(s.n_neg),
                          n_none=int(s.n_none), n_oob=int(s.n_oob), kernel_ms=float(s.kernel_ms),
                          batch_kernel_ms=float(st.kernel_ms))
+                if disc is not None:  # a ray may have ended on the disc: rays = n_pos + n_neg + n_none + n_disc
+                    d["n_disc"] = self.context.frame_disc_hits(len(out) - done_before)
                 out.append(d)
                 if on_frame is not None:
                     on_frame(k, frame, d)

@@ -323,6 +323,30 @@ class SphericalImage:
         return tuple(taps), tuple(raw), rc == 0
 
 
+class Disc:
+    """An accretion disc (not in the reference; include/curvis_hip.h has the definition): a thin annulus in the equatorial plane
+    between the radial coordinates l_inner < l_outer (in l, of either sign: a negative value lies on the far side of a wormhole),
+    textured with `image`, HxWx4 (RGBA8) or HxWx3 (RGB8, alpha := 255) -- W along azimuth, H along l.  Opaque where alpha >= 128,
+    absent elsewhere; it emits its texel's colour.  The ValueErrors are the refusals of curvis_ctx_set_disc."""
+
+    def __init__(self, image, l_inner, l_outer):
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
+            raise ValueError("image must be HxWx3 or HxWx4 uint8")
+        if img.shape[0] == 0 or img.shape[1] == 0:
+            raise ValueError("disc: empty texture")
+        if img.shape[2] == 3:
+            img = np.concatenate([img, np.full(img.shape[:2] + (1,), 255, np.uint8)], axis=2)
+        for v in (l_inner, l_outer):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+                raise ValueError("disc: l_inner and l_outer must be finite numbers")
+        if not float(l_inner) < float(l_outer):
+            raise ValueError("disc: l_inner must be less than l_outer")
+        self.rgba = np.ascontiguousarray(img)
+        self.height_pixels, self.width_pixels = self.rgba.shape[:2]
+        self.l_inner, self.l_outer = float(l_inner), float(l_outer)
+
+
 class HostBuffer:
     """page-locked host memory (curvis_host_alloc) as a uint8 numpy array `.array`: the device-to-host copy of a render
     into it is one DMA transfer instead of a staged copy through pageable memory"""
@@ -354,6 +378,7 @@ class Context:
         check(lib().curvis_ctx_create(int(device), C.byref(self._h)))
         self.device = device
         self._sky_objs = [None, None]  # strong refs: identity check must not suffer id() reuse
+        self._disc_obj = None          # the Disc bound by set_disc (same reason), or None
         self._async_download = False
         self._async_streams = False
         self._dl_keep = None  # the array the last download went (or is still going) into: see _downloaded
@@ -387,6 +412,28 @@ class Context:
                                        image.height_pixels), self._h)
         check(lib().curvis_ctx_set_sky_orientation(self._h, which, dptr(image.forward), dptr(image.up)), self._h)
         self._sky_objs[which] = image
+
+    def set_disc(self, disc):
+        """curvis_ctx_set_disc: the context's accretion disc (a Disc), or None to remove it.  While one is set the brute renderer
+        honours it and the efficient renderer, the direct renderer and the debug dump refuse to render."""
+        if disc is None:
+            check(lib().curvis_ctx_set_disc(self._h, None, 0, 0, 0.0, 0.0), self._h)
+        else:
+            if not isinstance(disc, Disc):
+                raise ValueError("disc must be a curvis_amd.Disc or None")
+            check(lib().curvis_ctx_set_disc(self._h, disc.rgba.ctypes.data, disc.width_pixels, disc.height_pixels, disc.l_inner,
+                                            disc.l_outer), self._h)
+        self._disc_obj = disc
+
+    def frame_disc_hits(self, frame=None):
+        """rays that ended on the disc in one frame (or the list for all frames) of the last render call (curvis_ctx_frame_disc_hits)"""
+        def one(k):
+            n = C.c_uint64(0)
+            check(lib().curvis_ctx_frame_disc_hits(self._h, k, C.byref(n)), self._h)
+            return int(n.value)
+        if frame is not None:
+            return one(int(frame))
+        return [one(k) for k in range(self.get_option("last_frames"))]
 
     def set_sky_device(self, which, dev_ptr, w, h, copy=False, forward=(1.0, 0.0, 0.0), up=(0.0, 0.0, 1.0)):
         check(lib().curvis_ctx_set_sky_device(self._h, which, C.c_void_p(dev_ptr), w, h, int(copy)), self._h)
@@ -912,9 +959,14 @@ class RelativisticSystem:
     multiple of 1/256, a ray's Euler step grows as |l| / L0 (library option "step_scale"); and integrator="euler" (the reference's
     forward Euler) or "heun" (not in the reference: Heun's method, second order, two Euler steps averaged; library option
     "integrator"); and sky_mipmap (False or True; not in the reference: with sky_filter="bilinear", the blend is taken on a mip
-    pyramid of the sky at the level of the ray's footprint among its neighbours; library option "sky_mipmap")."""
+    pyramid of the sky at the level of the ray's footprint among its neighbours; library option "sky_mipmap").
+    disc (a Disc or None; not in the reference): an accretion disc in the equatorial plane, seen by render_image with every keyword;
+    render_image_efficient, render_image_direct and render_image_debug raise ValueError while it is set."""
 
-    def __init__(self, metric, background_positive, background_negative, camera, context=None):
+    def __init__(self, metric, background_positive, background_negative, camera, context=None, disc=None):
+        if disc is not None and not isinstance(disc, Disc):
+            raise ValueError("disc must be a curvis_amd.Disc or None")
+        self.disc = disc
         self.metric = metric
         self.background_positive = background_positive
         # a SchwarzschildMetric without a -l background: the horizon is painted black
@@ -929,6 +981,13 @@ class RelativisticSystem:
             ctx.set_sky(0, self.background_positive)
         if ctx._sky_objs[1] is not self.background_negative:
             ctx.set_sky(1, self.background_negative)
+        # the disc as well, None included: a context shared between systems must not leak one system's disc into another's frame
+        if ctx._disc_obj is not self.disc:
+            ctx.set_disc(self.disc)
+
+    def _refuse_disc(self, what):
+        if self.disc is not None:
+            raise ValueError("a disc is set: %s cannot see it -- render_image (the per-pixel renderer) does" % what)
 
     def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
                      step_scale=0.0, integrator="euler", sky_mipmap=False):
@@ -948,6 +1007,7 @@ class RelativisticSystem:
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
+        self._refuse_disc("render_image_efficient reduces every ray to an equatorial orbit and")
         self._bind_skies()
         with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
             rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
@@ -962,6 +1022,7 @@ class RelativisticSystem:
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
+        self._refuse_disc("render_image_direct reduces every ray to an equatorial orbit and")
         self._bind_skies()
         with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
             rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
@@ -969,6 +1030,7 @@ class RelativisticSystem:
         return rgb
 
     def render_image_debug(self, max_iterations, max_radius, delta):
+        self._refuse_disc("render_image_debug shades from the ray store, which has no slot for a disc colour, and")
         self._bind_skies()
         rgb, st, dbg = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta,
                                                  debug=True)

@@ -107,6 +107,8 @@ typedef struct curvis_camera {
 
 /* PhotonEscape (src/systems.rs:39-44) */
 enum { CURVIS_NOT_ESCAPED = 0, CURVIS_POSITIVE_SPACE = 1, CURVIS_NEGATIVE_SPACE = -1 };
+/* not in the reference: the ray ended on the context's disc (below) */
+enum { CURVIS_DISC = 2 };
 
 /* per-ray final state, for parity tests: RelativisticObject (src/vectors.rs:135-139) after
  * escape_photon, number of Euler steps executed, escape code, raw texel indices
@@ -186,6 +188,54 @@ int curvis_ctx_read_sky(curvis_ctx *ctx, int which, size_t offset, size_t bytes,
  * is not there yet: *w x *h RGBA8 texels into `out` (NULL: the size alone).  CURVIS_E_NO_SKY without a sky, CURVIS_E_INVALID for a
  * level the chain does not have.  For tests and tools. */
 int curvis_ctx_sky_mip_level(curvis_ctx *ctx, int which, uint32_t level, uint8_t *out, uint32_t *w, uint32_t *h);
+
+/* The accretion disc (not in the reference): one object at finite distance, a thin textured annulus in the equatorial plane, seen by
+ * the brute renderer.  A context may hold one disc: an RGBA8 texture D of w x h texels, w along azimuth and h along l, and two finite
+ * doubles l_inner < l_outer of either sign.  The bounds are in the radial coordinate l, not in r(l): l is monotonic in every metric
+ * kind (the Schwarzschild kind's R(l) is not), and negative values put the disc on the far side of a wormhole.  The disc lies in the
+ * plane theta = pi/2 (mod pi), is infinitely thin, opaque where its texel's alpha is >= 128 and absent where it is < 128, and emits its
+ * texel's colour: no redshift, no Doppler shift, no beaming (see what the Schwarzschild paragraph says is not represented).
+ *
+ * Notation for a ray.  y_0 is the photon at the camera, y_k the state after k steps of whatever the call's step is (the Euler step,
+ * "step_scale"'s step, or a Heun step; the stage states of a Heun step are not states).  (s_k, c_k) is the one cv_math.h sincos
+ * evaluation of theta_k that the step from y_k performs anyway (under Heun: its first stage's).  It is defined only for states a step
+ * is taken from -- not escaped, and k < max_iterations: the final state of an escaping or capped ray is never tested.  The cosine of
+ * a double is never zero.
+ * For k >= 1, before the step from y_k is counted:
+ *   1. The ray crossed the plane iff (c_{k-1} < 0) != (c_k < 0).
+ *   2. t = c_{k-1} / (c_{k-1} - c_k), the correctly rounded quotient (IEEE `/` on the host, a Markstein form on the device -- never a
+ *      bare hardware seed).
+ *   3. l_hit = l_{k-1} + t (l_k - l_{k-1}) and phi_hit = phi_{k-1} + t (phi_k - phi_{k-1}), each operation individually rounded, in
+ *      that order, no fma.
+ *   4. The crossing is on the disc iff l_inner <= l_hit && l_hit <= l_outer (a NaN fails both compares).
+ *   5. If s_k < 0: phi_hit = phi_hit + pi.  A ray whose theta has left [0, pi] is physically at azimuth phi + pi -- what the sky
+ *      lookup's normalize_theta_phi does, with the same constant pi.
+ *   6. Column: tx = min(as_u32((rem_euclid(phi_hit, 2 pi) / (2 pi)) * (double)w), w - 1), with the sky lookup's rem_euclid and `as u32`
+ *      and a correctly rounded quotient.
+ *   7. Row: ty = min(as_u32(((l_hit - l_inner) / (l_outer - l_inner)) * (double)h), h - 1).
+ *   8. If alpha(D[ty][tx]) >= 128 the ray ends here: its code is CURVIS_DISC, its step count is k, its colour is the RGB of D[ty][tx].
+ *      It counts in rays and steps and in the per-frame counter n_disc (curvis_ctx_frame_disc_hits), and in none of n_pos, n_neg,
+ *      n_none, n_oob: per frame, rays = n_pos + n_neg + n_none + n_disc.
+ *   9. Otherwise the ray goes on as if nothing had been there.
+ * The colour goes where a sky colour goes: under "supersample" sub-rays on the disc are averaged with sub-rays on the sky;
+ * "sky_filter" does not filter it; under "sky_mipmap" a disc ray is a quad partner that saw no sky.  Steps 1-7 are one function for
+ * host and device (cv_device.h disc_crossing); curvis_disc_crossing is its host accessor.
+ *
+ * curvis_ctx_set_disc copies the texture (host memory, w * h * 4 bytes, row-major) to the device; rgba == NULL removes the disc.
+ * CURVIS_E_INVALID for w == 0, h == 0, a bound that is not finite, or !(l_inner < l_outer); the disc that was set before stays.  The
+ * disc belongs to the context: curvis_ctx_bcast_skies does not carry it.  While a disc is set, curvis_render_brute, _rows and _batch
+ * honour it, with every option, through the static kernel (never the relay kernel); refused with CURVIS_E_INVALID and a message that
+ * names the disc are curvis_render_efficient, curvis_render_efficient_batch, curvis_ctx_prefetch_efficient and curvis_render_direct
+ * (both renderers reduce every ray to an equatorial orbit that depends on one angle: there is no theta), curvis_render_brute_debug,
+ * "variant" = 0 and "fuse_shade" = 0 (the staged paths have no slot for a disc colour).  curvis_photon_trajectories,
+ * curvis_compute_escape_angles and curvis_walk_ray do not see it.  With no disc set every call launches exactly the kernels it
+ * launched before there was one. */
+int curvis_ctx_set_disc(curvis_ctx *ctx, const uint8_t *rgba, uint32_t w, uint32_t h, double l_inner, double l_outer);
+/* Steps 1-7 above for one pair of consecutive states, on the host (no GPU needed): *hit = 1 when the ray crossed the plane inside
+ * [l_inner, l_outer], and then (*tx, *ty) is the texel; *hit = 0 otherwise (tx, ty = 0).  The alpha test of step 8 is the caller's.
+ * CURVIS_E_INVALID for a null pointer, w == 0 or h == 0; the bounds are taken as they are. */
+int curvis_disc_crossing(double c_prev, double c_cur, double s_cur, double l_prev, double l_cur, double phi_prev, double phi_cur,
+                         double l_inner, double l_outer, uint32_t w, uint32_t h, int32_t *hit, uint32_t *tx, uint32_t *ty);
 
 /* how two devices of this node are connected (hipExtGetLinkTypeAndHopCount, hipDeviceCanAccessPeer, hipDeviceGetP2PAttribute):
  * link_type = HSA_AMD_LINK_INFO_TYPE_* (2 PCIe, 4 xGMI; 0 with hops 0 for a == b; -1 unknown).  Read beside the measured
@@ -366,6 +416,9 @@ int curvis_ctx_sampling_info(const curvis_ctx *ctx, uint32_t frame, curvis_sampl
  * escape space); the *_ms fields are the frame's share of the launch time (by executed steps), not a separate
  * measurement.  "last_frames" (curvis_ctx_get_option) = number of frames available. */
 int curvis_ctx_frame_stats(const curvis_ctx *ctx, uint32_t frame, curvis_stats *stats);
+/* n_disc of frame `frame` of the last render call, like curvis_ctx_frame_stats: the rays that ended on the disc (0 for a render
+ * without a disc, and for the efficient and the direct renderer). */
+int curvis_ctx_frame_disc_hits(const curvis_ctx *ctx, uint32_t frame, uint64_t *n_disc);
 /* the (alpha, escape angle, escape space) table of a frame of the last efficient render; cap >= n_samples */
 int curvis_ctx_samples(const curvis_ctx *ctx, uint32_t frame, double *alpha, double *escape_angle,
                        double *escape_space, size_t cap);
