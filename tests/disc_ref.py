@@ -333,16 +333,31 @@ def disc_texture():
     return _cache["tex"]
 
 
+def scene_from(kind, pos, fwd, up, focal, res, l_range, product_res=None):
+    """a scene from explicit parameters: (kind, oracle metric, product metric, oracle camera, product camera, Disc).  The Schwarzschild
+    kind has no oracle metric (None): its rays are walked by HostStepper.  product_res: the product camera's resolution where it is not
+    the oracle camera's (a supersampled call: the oracle camera is the fine grid's)"""
+    import curvis_amd
+    if kind == "schwarzschild":
+        om, pm = None, curvis_amd.SchwarzschildMetric(SCHW_MASS)
+    else:
+        om, pm = SR.metrics(kind)
+    pres = product_res or res
+    return (kind, om, pm, O.camera(pos, fwd, up, focal, DIAG, res), curvis_amd.Camera(pos, fwd, up, focal, DIAG, pres[0], pres[1]),
+            Disc(disc_texture(), l_range[0], l_range[1]))
+
+
+def stepper_of(om, pm):
+    """the stepper that walks a scene_from scene's rays"""
+    return HostStepper(pm) if om is None else OracleStepper(om)
+
+
 def scene(name, res=None, phi=None):
     """(kind, oracle metric, product metric, oracle camera, product camera, Disc)"""
-    import curvis_amd
-    kind, pos, fwd, up, focal, res0, (l_in, l_out) = SCENES[name]
-    res = res or res0
+    kind, pos, fwd, up, focal, res0, l_range = SCENES[name]
     if phi is not None:
         pos = pos[:3] + (phi,)
-    om, pm = SR.metrics(kind)
-    return (kind, om, pm, O.camera(pos, fwd, up, focal, DIAG, res), curvis_amd.Camera(pos, fwd, up, focal, DIAG, res[0], res[1]),
-            Disc(disc_texture(), l_in, l_out))
+    return scene_from(kind, pos, fwd, up, focal, res or res0, l_range)
 
 
 def scene_rays(name, S=0, integrator=0, projection=P.PERSPECTIVE, res=None, disc=True, phi=None, delta=DELTA):
@@ -390,6 +405,7 @@ def assert_classes(rays, who, sneg_in_range=0):
 
 # ---- the Schwarzschild scene --------------------------------------------------------------------------------------------------------
 SCHW_MASS, SCHW_L_CAM, SCHW_THETA, SCHW_L_OUT, SCHW_RES, SCHW_FOCAL = 1.0, 8.0, 1.25, 14.0, (24, 16), 15.0
+SCHW_POS, SCHW_FWD, SCHW_UP = (0.0, SCHW_L_CAM, SCHW_THETA, 0.0), (-1.0, 0.0, -0.05), (0.0, 0.0, 1.0)
 
 
 def schwarzschild_scene():
@@ -397,7 +413,7 @@ def schwarzschild_scene():
     (product metric, oracle camera, product camera, Disc)"""
     import curvis_amd
     pm = curvis_amd.SchwarzschildMetric(SCHW_MASS)
-    pos, fwd, up = (0.0, SCHW_L_CAM, SCHW_THETA, 0.0), (-1.0, 0.0, -0.05), (0.0, 0.0, 1.0)
+    pos, fwd, up = SCHW_POS, SCHW_FWD, SCHW_UP
     return (pm, O.camera(pos, fwd, up, SCHW_FOCAL, DIAG, SCHW_RES),
             curvis_amd.Camera(pos, fwd, up, SCHW_FOCAL, DIAG, SCHW_RES[0], SCHW_RES[1]), Disc(disc_texture(), pm.l_of_radius(6.0 * SCHW_MASS), SCHW_L_OUT))
 
