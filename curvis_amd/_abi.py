@@ -66,6 +66,9 @@ SYMBOLS = {
     "curvis_disc_crossing": (C.c_int, [C.c_double] * 9 + [C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32),
                                                            C.POINTER(C.c_uint32)]),
     "curvis_ctx_frame_disc_hits": (C.c_int, [_vp, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "curvis_ctx_set_disc_motion": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "curvis_disc_shift": (C.c_int, [C.POINTER(Metric), C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, _dp]),
+    "curvis_disc_shade": (C.c_int, [C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]),
     "curvis_rccl_unique_id": (C.c_int, [_vp]),
     "curvis_ctx_rccl_comm_init": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "curvis_rccl_comm_destroy": (C.c_int, [_vp]),

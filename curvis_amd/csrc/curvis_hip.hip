@@ -533,6 +533,27 @@ int curvis_schwarzschild_u(const curvis_metric *m, double l, double *u) {
   return CURVIS_OK;
 }
 
+int curvis_ctx_set_disc_motion(curvis_ctx *ctx, int motion, double gain) {
+  if (!ctx) return CURVIS_E_INVALID;
+  if (motion < -1 || motion > 1) return fail(ctx, CURVIS_E_INVALID, "disc motion: must be 0 (static), 1 (prograde, +phi) or -1 (retrograde)");
+  if (!std::isfinite(gain) || gain < 0.0) return fail(ctx, CURVIS_E_INVALID, "disc motion: the gain must be finite and not negative");
+  ctx->disc_motion = motion, ctx->disc_gain = gain;
+  return CURVIS_OK;
+}
+
+int curvis_disc_shift(const curvis_metric *m, double l_hit, double l_camera, int motion, double gain, double p_phi, double *F) {
+  if (!m || !F || m->kind != CURVIS_METRIC_SCHWARZSCHILD || motion < -1 || motion > 1) return CURVIS_E_INVALID;
+  if (curvis_metric_validate(m) != CURVIS_OK) return CURVIS_E_METRIC;
+  *F = motion == 0 ? 1.0 : cvk::disc_shift(make_metric(*m), l_hit, l_camera, (double)motion, gain, p_phi);
+  return CURVIS_OK;
+}
+
+int curvis_disc_shade(uint32_t texel, double F, uint32_t *out) {
+  if (!out) return CURVIS_E_INVALID;
+  *out = cvk::disc_shade(texel, F);
+  return CURVIS_OK;
+}
+
 int curvis_metric_tensor(const curvis_metric *m, const double position[4], double g_cov[4], double g_contr[4]) {
   if (!m || !position) return CURVIS_E_INVALID;
   double r2;

@@ -794,8 +794,9 @@ CV_HD double rem_euclid_pos(double a, double b) {
  * quotients are the correctly rounded ones: t and the column's through cv_div_nr (operands a cosine apart resp. an angle below 2 pi
  * over a constant: far inside the range where its Markstein form is exact), the row's through the operator, whose operands are the
  * caller's bounds and may sit anywhere in the exponent range.  A NaN anywhere fails the range compare. */
-CV_HD bool disc_crossing(double c_prev, double c_cur, double s_cur, double l_prev, double l_cur, double ph_prev, double ph_cur, double l_in,
-                         double l_out, unsigned w, unsigned h, unsigned *tx, unsigned *ty) {
+/* disc_crossing_at hands out step 3's l_hit as well (written where the crossing is on the disc): the emission shift below needs it. */
+CV_HD bool disc_crossing_at(double c_prev, double c_cur, double s_cur, double l_prev, double l_cur, double ph_prev, double ph_cur, double l_in,
+                            double l_out, unsigned w, unsigned h, unsigned *tx, unsigned *ty, double *l_at) {
   if ((c_prev < 0.0) == (c_cur < 0.0)) return false;                    /* 1 */
   const double t = cv_div_nr(c_prev, c_prev - c_cur);                   /* 2 */
   const double dl = l_cur - l_prev, dph = ph_cur - ph_prev;
@@ -808,7 +809,53 @@ CV_HD bool disc_crossing(double c_prev, double c_cur, double s_cur, double l_pre
   const unsigned y = rust_as_u32(((l_hit - l_in) / (l_out - l_in)) * (double)h);                 /* 7 */
   *tx = x < w - 1u ? x : w - 1u;
   *ty = y < h - 1u ? y : h - 1u;
+  *l_at = l_hit;
   return true;
+}
+CV_HD bool disc_crossing(double c_prev, double c_cur, double s_cur, double l_prev, double l_cur, double ph_prev, double ph_cur, double l_in,
+                         double l_out, unsigned w, unsigned h, unsigned *tx, unsigned *ty) {
+  double l_hit;
+  return disc_crossing_at(c_prev, c_cur, s_cur, l_prev, l_cur, ph_prev, ph_cur, l_in, l_out, w, h, tx, ty, &l_hit);
+}
+
+/* ---- the disc's emission shift (include/curvis_hip.h has the definition; the lines below are its steps 1-8 in its order, every operation
+ * individually rounded, no fma).  One text for host and device: the DISC = 2 kernels call disc_shift_at and disc_shade inside the
+ * crossing branch, at the moment a lane gets its texel; curvis_disc_shift and curvis_disc_shade are the host accessors.  The camera's
+ * half of the ratio (steps 1 and 6 for l_camera) depends on the frame alone: the host evaluates disc_camera_factor once per frame and
+ * the kernels read the result, so no lane solves the tortoise equation a second time.
+ * The quotients are the correctly rounded ones.  Steps 3, 4 and 6 through the operator: their operands scale with the caller's l and M
+ * (w grows like l / 2M, the numerator of step 4 is 1/2M itself) and may sit anywhere in the exponent range.  Step 7 through cv_div_nr:
+ * behind steps 2 and 5, a = n / 2w lies in [2^-55, 1) (n >= one ulp of 1 where it is positive, and then w is next to 3/2; a -> 1 for
+ * large w), A_c in [0.21, 1] (u >= 0.278, the root of u + ln u = -1, at every l) and den in [2^-53, 2] for the p_phi of a traced ray, so
+ * the divisor lies in [2^-109, 4] and the quotient in [2^-57, 2^112]: far inside the range where its Markstein form is exact. */
+CV_HD double disc_camera_factor(const MetricParams &M, double l_camera) {
+  const double u_c = schwarzschild_u(M, l_camera);                      /* 1 */
+  return u_c / (1.0 + u_c);                                             /* 6 */
+}
+/* sigma is the motion as a double, +1.0 or -1.0: the product sigma * om is exact */
+CV_HD double disc_shift_at(const MetricParams &M, double l_hit, double A_c, double sigma, double gain, double p_phi) {
+  const double u_e = schwarzschild_u(M, l_hit);                         /* 1 */
+  const double w = 1.0 + u_e, n = 2.0 * u_e - 1.0;                      /* 2 */
+  if (!(n > 0.0)) return 0.0;
+  const double a = n / (2.0 * w);                                       /* 3 */
+  const double om = M.inv_pim / (w * CV_SQRT(2.0 * w));                 /* 4 */
+  const double den = 1.0 + (sigma * om) * p_phi;                        /* 5 */
+  if (!(den > 0.0)) return 0.0;
+  const double g2 = cv_div_nr(a, A_c * (den * den));                    /* 7 */
+  return gain * (g2 * g2);                                              /* 8 */
+}
+CV_HD double disc_shift(const MetricParams &M, double l_hit, double l_camera, double sigma, double gain, double p_phi) {
+  return disc_shift_at(M, l_hit, disc_camera_factor(M, l_camera), sigma, gain, p_phi);
+}
+/* the colour: the three channels of an RGBA8 texel scaled by F and rounded to nearest, saturating; alpha kept */
+CV_HD unsigned disc_shade(unsigned texel, double F) {
+  unsigned out = texel & 0xFF000000u;
+  for (int k = 0; k < 3; ++k) {
+    const double v = (double)((texel >> (8 * k)) & 0xFFu) * F + 0.5;
+    const unsigned c = (v >= 255.0) ? 255u : rust_as_u32(v);
+    out |= c << (8 * k);
+  }
+  return out;
 }
 
 struct SkyParams {

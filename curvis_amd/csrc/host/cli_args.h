@@ -26,12 +26,18 @@ struct Args {
                        the radial coordinates L; all three or none, and --mode brute, the one renderer that sees it */
   std::string disc_inner_s, disc_outer_s;
   double disc_inner = 0.0, disc_outer = 0.0;
+  std::string disc_motion_s, disc_gain_s; /* --disc-motion static|prograde|retrograde --disc-gain G: the disc's emission shift
+                                             (curvis_ctx_set_disc_motion); with --disc only, a motion only under a metric file with `mass` */
+  int disc_motion = 0;
+  double disc_gain = 1.0;
 };
 /* the disc of the run (Args::disc, decoded by load_common) for make_ctx_bare: every context gets it */
 struct DiscOfRun {
   bool set = false;
   pngio::Image img;
   double l_inner = 0.0, l_outer = 0.0;
+  int motion = 0;
+  double gain = 1.0;
 } g_disc;
 int g_supersample = 1; /* Args::supersample for make_ctx_bare: every context of the run gets it */
 int g_sky_filter = 0;  /* Args::sky_filter, likewise */
@@ -55,7 +61,8 @@ void usage() {
       "              [--contexts-per-device C] [--supersample 1|2|4|8] [--sky-filter nearest|bilinear]\n"
       "              [--projection perspective|equirectangular|fisheye] [--step-scale L0]\n"
       "              [--integrator euler|heun] [--sky-mipmap on|off]\n"
-      "              [--disc <IMAGE FILE> --disc-inner L --disc-outer L]  (an accretion disc; needs --mode brute)\n");
+      "              [--disc <IMAGE FILE> --disc-inner L --disc-outer L]  (an accretion disc; needs --mode brute)\n"
+      "              [--disc-motion static|prograde|retrograde] [--disc-gain G]  (with --disc; a motion needs a metric file with `mass`)\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -140,6 +147,8 @@ Args parse_args(int argc, char **argv) {
     else if (key == "--disc") take(a.disc);
     else if (key == "--disc-inner") take(a.disc_inner_s);
     else if (key == "--disc-outer") take(a.disc_outer_s);
+    else if (key == "--disc-motion") take(a.disc_motion_s);
+    else if (key == "--disc-gain") take(a.disc_gain_s);
     else if (key == "-h" || key == "--help") { usage(); std::exit(0); }
     else if (!s.empty() && s[0] == '-') die("error: unexpected argument '" + s + "' found", 2);
     else pos.push_back(s);
@@ -167,6 +176,19 @@ Args parse_args(int argc, char **argv) {
       die("error: --disc-inner and --disc-outer must be finite numbers, the inner one less than the outer", 2);
     /* no silent change of mode: the efficient and the direct renderer reduce every ray to an equatorial orbit and cannot see a disc */
     if (a.mode != "brute") die("error: --disc needs --mode brute (the per-pixel renderer is the one that sees a disc); this run is --mode " + a.mode, 2);
+  }
+  if (!a.disc_motion_s.empty() || !a.disc_gain_s.empty()) {
+    if (a.disc.empty()) die("error: --disc-motion and --disc-gain need --disc (they say how the disc emits)", 2);
+    if (!a.disc_motion_s.empty()) {
+      if (a.disc_motion_s != "static" && a.disc_motion_s != "prograde" && a.disc_motion_s != "retrograde")
+        die("error: --disc-motion must be static, prograde or retrograde", 2);
+      a.disc_motion = a.disc_motion_s == "prograde" ? 1 : a.disc_motion_s == "retrograde" ? -1 : 0;
+    }
+    if (!a.disc_gain_s.empty()) {
+      char *end = nullptr;
+      a.disc_gain = std::strtod(a.disc_gain_s.c_str(), &end);
+      if (*end != '\0' || !std::isfinite(a.disc_gain) || a.disc_gain < 0.0) die("error: --disc-gain must be a finite number, not negative", 2);
+    }
   }
   if (a.sky_broadcast != "rccl" && a.sky_broadcast != "upload") die("error: --sky-broadcast must be rccl or upload", 2);
   if (a.gpu_png != "auto" && a.gpu_png != "on" && a.gpu_png != "off") die("error: --gpu-png must be auto, on or off", 2);
@@ -261,6 +283,9 @@ void load_common(const Args &a_in, Common &c, const char *what) {
   if (curvis_metric_validate(&c.metric) != CURVIS_OK)
     die(std::string("Error in rendering ") + what + ": metric parameters must be positive (src/metrics.rs:409-456)", 101);
   if (!validate(c.cam, err) || !validate(c.sim, err)) die(std::string("Error in rendering ") + what + ": " + err);
+  /* a disc's motion is Keplerian: a hole only (the library refuses the render call; this says so before anything is decoded) */
+  if (a.disc_motion != 0 && c.metric.kind != CURVIS_METRIC_SCHWARZSCHILD)
+    die("error: --disc-motion " + a.disc_motion_s + " needs a metric file with `mass` (-m: a Schwarzschild hole); in the other metrics free matter is at rest and nothing orbits", 2);
   /* both backgrounds are decoded at the same time (an 8192x4096 PNG takes the better part of a second to inflate and
    * unfilter); errors are reported in the reference's order, image 1 first */
   std::string err2;
@@ -301,6 +326,7 @@ void load_common(const Args &a_in, Common &c, const char *what) {
     need(a.disc, "disc image");
     if (!jpegio::load_image(a.disc, g_disc.img, err)) die(std::string("Error in rendering ") + what + ": disc image: " + err);
     g_disc.l_inner = a.disc_inner, g_disc.l_outer = a.disc_outer;
+    g_disc.motion = a.disc_motion, g_disc.gain = a.disc_gain;
     g_disc.set = true;
   }
 }
@@ -334,6 +360,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
   if (g_step_scale != 0) check(curvis_ctx_set_option(ctx, "step_scale", g_step_scale), ctx, what);
   if (g_integrator != 0) check(curvis_ctx_set_option(ctx, "integrator", g_integrator), ctx, what);
   if (g_disc.set) check(curvis_ctx_set_disc(ctx, g_disc.img.rgba.data(), g_disc.img.w, g_disc.img.h, g_disc.l_inner, g_disc.l_outer), ctx, what);
+  if (g_disc.set && (g_disc.motion != 0 || g_disc.gain != 1.0)) check(curvis_ctx_set_disc_motion(ctx, g_disc.motion, g_disc.gain), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {

@@ -192,6 +192,15 @@ template <typename Base>
 struct WithDisc : Base {
   DiscArgs disc;
 };
+/* ---- the disc's emission shift (include/curvis_hip.h, curvis_ctx_set_disc_motion): appended behind the disc for the DISC = 2 kernels */
+struct DiscMotionArgs {
+  double sigma, gain;       /* the motion as +1.0 or -1.0, and G */
+  const double *cam_factor; /* device, one per frame of the launch: cv_device.h disc_camera_factor of the frame's camera, from the host */
+};
+template <typename Base>
+struct WithDiscMotion : Base {
+  DiscMotionArgs motion;
+};
 /* Called by EVERY lane of a wave that holds one 8x8 tile of rays whose origin is even in both absolute ray coordinates: `which` is 0
  * (no sky: capped, or outside the frame), 1 (+l sky) or 2 (-l sky), (Xc, Yc) the lane's indices on its own sky.  The lanes exchange the
  * three with the horizontal (lane ^ 1) and vertical (lane ^ 8) partner of their 2 x 2 quad on DPP, form the footprint, the level and

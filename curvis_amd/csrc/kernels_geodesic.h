@@ -49,9 +49,11 @@ using IntegrateArgs = std::conditional_t<ADAPT != 0, IntegrateParamsAdapt, Integ
 /* FILTER = 2 (option "sky_mipmap"): either of the two with the skies' level tables appended (kernels_epilogue.h WithSkyMip) */
 template <int ADAPT, int FILTER>
 using IntegrateArgsF = std::conditional_t<FILTER == 2, WithSkyMip<IntegrateArgs<ADAPT>>, IntegrateArgs<ADAPT>>;
-/* DISC = 1 (a disc is set, include/curvis_hip.h): any of the four with the disc appended (kernels_epilogue.h WithDisc) */
+/* DISC = 1 (a disc is set, include/curvis_hip.h): any of the four with the disc appended (kernels_epilogue.h WithDisc);
+ * DISC = 2 (the disc has a motion): that with the motion appended (WithDiscMotion) */
 template <int ADAPT, int FILTER, int DISC>
-using IntegrateArgsD = std::conditional_t<DISC != 0, WithDisc<IntegrateArgsF<ADAPT, FILTER>>, IntegrateArgsF<ADAPT, FILTER>>;
+using IntegrateArgsD = std::conditional_t<DISC == 2, WithDiscMotion<WithDisc<IntegrateArgsF<ADAPT, FILTER>>>,
+                                          std::conditional_t<DISC != 0, WithDisc<IntegrateArgsF<ADAPT, FILTER>>, IntegrateArgsF<ADAPT, FILTER>>>;
 
 struct ShadeParams {
   cvk::MetricParams metric;
@@ -196,23 +198,60 @@ struct DiscProbe {
     l_prev = q.l, ph_prev = q.ph, c_prev = c;
   }
 };
+/* The probe of the DISC = 2 kernels (the disc has a motion, include/curvis_hip.h): DiscProbe with the emission shift at the moment a lane
+ * gets its texel.  What the lane keeps is the SHADED colour, so the loop carries nothing DiscProbe's does not.  Behind the two branches:
+ * cv_device.h disc_shift_at (one tortoise solve for u_e, three divisions and a root) with the ray's constant p_phi and the camera factor
+ * of the wave's frame -- a tile never straddles frames, so the frame is wave-uniform, found from the block index as the epilogue finds it,
+ * and the factor is one load of what the host evaluated per frame. */
+struct DiscShiftProbe {
+  const DiscArgs &D;
+  const DiscMotionArgs &S;
+  const cvk::MetricParams &M;
+  unsigned rays_per_frame;
+  const cvk::Ray &q;
+  double &l_prev, &ph_prev, &c_prev;
+  unsigned &texel;
+  bool first;
+  __device__ __forceinline__ void rec(int, double, double, double) const {}
+  __device__ __forceinline__ void sincos(double s, double c) const {
+    const bool crossed = !first & ((c_prev < 0.0) != (c < 0.0));
+    if (__builtin_amdgcn_ballot_w64(crossed)) {
+      if (crossed) {
+        unsigned tx, ty;
+        double l_hit;
+        if (cvk::disc_crossing_at(c_prev, c, s, l_prev, q.l, ph_prev, q.ph, D.l_in, D.l_out, D.w, D.h, &tx, &ty, &l_hit)) {
+          const unsigned t = D.texels[(size_t)ty * D.w + tx];
+          if ((t >> 24) >= 128u) {
+            const unsigned frame = frame_of_tile(((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, rays_per_frame);
+            texel = cvk::disc_shade(t, cvk::disc_shift_at(M, l_hit, S.cam_factor[frame], S.sigma, S.gain, q.p3));
+          }
+        }
+      }
+    }
+    l_prev = q.l, ph_prev = q.ph, c_prev = c;
+  }
+};
 }  // namespace
 template <>
 struct cvk::probe_takes_sincos<DiscProbe> {
   static constexpr bool value = true;
 };
+template <>
+struct cvk::probe_takes_sincos<DiscShiftProbe> {
+  static constexpr bool value = true;
+};
 namespace {
 /* a step of a DISC kernel: the call's step flavour with phi integrated, under the probe (with Heun, the first stage's) */
-template <int KIND, bool FAST, bool HEUN>
-__device__ __forceinline__ void disc_step(const cvk::MetricParams &M, double delta, cvk::Ray &q, bool lane_ok, const DiscProbe &probe) {
+template <int KIND, bool FAST, bool HEUN, class PROBE>
+__device__ __forceinline__ void disc_step(const cvk::MetricParams &M, double delta, cvk::Ray &q, bool lane_ok, const PROBE &probe) {
   constexpr bool W = MathTablesLds<KIND>::WIDE_SC;
   if constexpr (HEUN) {
     static_assert(FAST, "the Heun step exists for the fast step only");
-    cvk::ray_step_heun<KIND, true, true, W, false, DiscProbe>(M, q, delta, lane_ok, probe);
+    cvk::ray_step_heun<KIND, true, true, W, false, PROBE>(M, q, delta, lane_ok, probe);
   } else if constexpr (FAST) {
-    cvk::ray_step_fast<KIND, true, W, false, DiscProbe>(M, q, delta, lane_ok, probe);
+    cvk::ray_step_fast<KIND, true, W, false, PROBE>(M, q, delta, lane_ok, probe);
   } else {
-    cvk::ray_step_probed<KIND, true, W, DiscProbe>(M, q, delta, probe);
+    cvk::ray_step_probed<KIND, true, W, PROBE>(M, q, delta, probe);
   }
 }
 
@@ -316,7 +355,8 @@ __global__ __launch_bounds__(256) void geodesic_persistent(const IntegrateParams
  * still fit 7 waves (71-72 VGPRs) -- all but the strict step under the mip-mapped epilogue, which spilled 16 bytes there in a trial build (73 VGPRs at 6) -- and every
  * Schwarzschild form its budget (79-80 of 96, Heun 94 of 128); the Interstellar Euler forms would spill at 5 waves (they take up to 104 at 4), the
  * Ellis Heun forms at 6 (87 at 5) and the flat ones at 7 (up to 73 at 6); the Interstellar Heun forms fit the 4 waves they have (115-117 of 128).
- * With these, no DISC kernel uses scratch. */
+ * With these, no DISC kernel uses scratch.  The DISC = 2 forms (Schwarzschild alone) take their parents' registers, 80 and Heun 94, and need
+ * no entry of their own (profiles/disc_motion_asm_diff.txt). */
 constexpr int disc_wave_cost(int kind, int adapt, bool fast, int filter) {
   if (kind == cvk::METRIC_SCHWARZSCHILD) return 0;
   if (kind == cvk::METRIC_INTERSTELLAR) return adapt == 2 ? 0 : 1;
@@ -333,11 +373,14 @@ template <int KIND, bool PHI, bool FAST, bool FUSED, int SS = 1, int FILTER = 0,
   DISC: 1 while the context holds a disc (include/curvis_hip.h; FUSED, and the one fused form that integrates phi): the loop keeps l, phi
   and cos(theta) of the previous state, tests the sign of the cosine each step hands out -- a ballot and a scalar branch -- and, inside the
   branch, calls cv_device.h disc_crossing, gathers the texel and ends the ray where it is opaque; four register pairs and a dword more
-  than the parent's loop, which costs some of the DISC kernels a wave (disc_wave_cost) */
+  than the parent's loop, which costs some of the DISC kernels a wave (disc_wave_cost); 2 while that disc has a motion
+  (curvis_ctx_set_disc_motion; the Schwarzschild kind alone): the texel is scaled by the emission shift inside the same branch
+  (DiscShiftProbe), and the loop carries what DISC = 1 carries */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((kind_has_log(KIND) ? 5 : 7) - (ADAPT == 2 ? 1 : 0) - (DISC ? disc_wave_cost(KIND, ADAPT, FAST, FILTER) : 0))))
 void geodesic_static(const IntegrateArgsD<ADAPT, FILTER, DISC> P) { /* the Heun step holds the saved state across two stages, four register pairs more:
   at 7 (5) waves the loop would spill them, so the ADAPT = 2 kernels ask for one wave less */
   static_assert(DISC == 0 || (FUSED && PHI), "the disc exists in the fused kernels, which then integrate phi");
+  static_assert(DISC != 2 || KIND == cvk::METRIC_SCHWARZSCHILD, "a disc's motion is Keplerian: the Schwarzschild kind alone");
   static_assert(SS == 1 || (FUSED && (!PHI || DISC)), "supersampling resolves in the fused epilogue");
   static_assert(FILTER == 0 || (FUSED && (!PHI || DISC)), "the filtered lookup exists in the fused epilogues only");
   static_assert(PROJ == 0 || (FUSED && (!PHI || DISC)), "the projections exist in the fused kernels only");
@@ -382,7 +425,10 @@ void geodesic_static(const IntegrateArgsD<ADAPT, FILTER, DISC> P) { /* the Heun 
       for (;;) {
         double dk = P.delta;
         if constexpr (ADAPT != 0) dk = cvk::step_delta(P.delta, P.kappa, q.l);
-        disc_step<KIND, FAST, ADAPT == 2>(M, dk, q, lane_ok_w, DiscProbe{P.disc, q, l_prev, ph_prev, c_prev, disc_texel, k == 0u});
+        if constexpr (DISC == 2) /* the disc has a motion: the texel is shaded where it is found */
+          disc_step<KIND, FAST, ADAPT == 2>(M, dk, q, lane_ok_w, DiscShiftProbe{P.disc, P.motion, M, P.rays_per_frame, q, l_prev, ph_prev, c_prev, disc_texel, k == 0u});
+        else
+          disc_step<KIND, FAST, ADAPT == 2>(M, dk, q, lane_ok_w, DiscProbe{P.disc, q, l_prev, ph_prev, c_prev, disc_texel, k == 0u});
         ++k;
         const bool hit = disc_texel != 0u;
         const bool esc = hit | ray_escaped(q.l, P.max_radius);

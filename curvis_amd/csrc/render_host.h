@@ -28,6 +28,12 @@ struct curvis_ctx {
   bool disc_set = false;
   unsigned disc_w = 0, disc_h = 0;
   double disc_l_in = 0.0, disc_l_out = 0.0;
+  /* the disc's emission shift (curvis_ctx_set_disc_motion): the context's, whether a disc is set or not; with a motion the brute
+   * renderer launches the DISC = 2 kernels, which read one camera factor per frame (cv_device.h disc_camera_factor, evaluated here) */
+  int disc_motion = 0;
+  double disc_gain = 1.0;
+  DeviceBuffer<double> d_disc_cam;
+  PinnedBuffer<double> h_disc_cam;
   std::vector<uint64_t> last_frame_disc; /* rays that ended on the disc, per frame of the last brute render (curvis_ctx_frame_disc_hits) */
   /* frame resources */
   DeviceBuffer<unsigned char> d_fb;
@@ -646,11 +652,17 @@ int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused
 
 /* A disc is set: the DISC form of the fused static kernel, its argument the plain form's with the disc appended.  Every call shape
  * that reaches here has one (render_impl refuses the debug dump, variant = 0 and fuse_shade = 0 while a disc is set). */
-template <int KIND, bool FAST, int SS, int FILTER, int PROJ, int ADAPT>
+template <int KIND, bool FAST, int SS, int FILTER, int PROJ, int ADAPT, int DISC = 1>
 int launch_disc(curvis_ctx *ctx, const IntegrateParamsAdapt &PA) {
   const unsigned bt = integrate_block_threads(ctx, KIND);
   const dim3 grid((unsigned)((PA.total_rays + bt - 1ull) / bt));
-  IntegrateArgsD<ADAPT, FILTER, 1> PD;
+  IntegrateArgsD<ADAPT, FILTER, DISC> PD;
+  if constexpr (DISC == 2) { /* the disc has a motion: sigma, G and the camera factors of the launch's frames (render_rays filled them) */
+    PD.motion.sigma = (double)ctx->disc_motion;
+    PD.motion.gain = ctx->disc_gain;
+    const cvk::CameraParams *cams0 = ctx->d_cams;
+    PD.motion.cam_factor = ctx->d_disc_cam + (PA.cams - cams0); /* the chunk's first frame, as PA.cams is */
+  }
   static_cast<IntegrateArgs<ADAPT> &>(PD) = PA;
   if constexpr (FILTER == 2) PD.mip = sky_mip_args(ctx);
   PD.disc.texels = ctx->d_disc;
@@ -658,7 +670,7 @@ int launch_disc(curvis_ctx *ctx, const IntegrateParamsAdapt &PA) {
   PD.disc.h = ctx->disc_h;
   PD.disc.l_in = ctx->disc_l_in;
   PD.disc.l_out = ctx->disc_l_out;
-  hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, true, SS, FILTER, PROJ, ADAPT, 1>), grid, dim3(bt), 0, ctx->stream, PD);
+  hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, true, SS, FILTER, PROJ, ADAPT, DISC>), grid, dim3(bt), 0, ctx->stream, PD);
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
 }
@@ -669,6 +681,8 @@ int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fu
                          uint32_t filter, int adapt) {
   return with_launch_shape(kind, fast, ss, filter, (uint32_t)P.projection, adapt, [&](auto S) {
     using T = decltype(S);
+    if constexpr (T::KIND == cvk::METRIC_SCHWARZSCHILD) /* a motion: the DISC = 2 form, which exists for this kind alone (render_impl refuses the others) */
+      if (ctx->disc_set && ctx->disc_motion != 0) return launch_disc<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT, 2>(ctx, P);
     if (ctx->disc_set) return launch_disc<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>(ctx, P);
     if constexpr (T::SS == 1 && T::FILTER == 0 && T::PROJ == 0)
       if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0, 0, T::ADAPT>(ctx, P, false, 0);
@@ -1068,6 +1082,12 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, sizeof(cvk::CameraParams) * c.n_frames, hipMemcpyHostToDevice, ctx->stream));
 
   const cvk::MetricParams MP = make_metric(*c.metric);
+  if (ctx->disc_set && ctx->disc_motion != 0) { /* the camera's half of the emission shift, once per frame, by the one shared function */
+    if ((rc = ctx->d_disc_cam.reserve(ctx, c.n_frames))) return rc;
+    if ((rc = ctx->h_disc_cam.reserve(ctx, c.n_frames))) return rc;
+    for (uint32_t f = 0; f < c.n_frames; ++f) ctx->h_disc_cam[f] = cvk::disc_camera_factor(MP, c.cams[f].pos[1]);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_disc_cam, ctx->h_disc_cam, sizeof(double) * c.n_frames, hipMemcpyHostToDevice, ctx->stream));
+  }
   RenderTotals tot;
   ctx->last_frame_stats.assign(c.n_frames, curvis_stats{});
   ctx->last_frame_disc.assign(c.n_frames, 0);
@@ -1119,6 +1139,8 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
     if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "a disc is set: the debug dump shades from the ray store, which has no slot for a disc colour (remove the disc: curvis_ctx_set_disc with rgba = NULL)");
     if (ctx->variant == 0) return fail(ctx, CURVIS_E_INVALID, "a disc is set: variant = 0 (the persistent kernel) shades from the ray store, which has no slot for a disc colour");
     if (ctx->fuse_shade == 0) return fail(ctx, CURVIS_E_INVALID, "a disc is set: fuse_shade = 0 shades from the ray store, which has no slot for a disc colour");
+    if (ctx->disc_motion != 0 && metric && metric->kind != CURVIS_METRIC_SCHWARZSCHILD)
+      return fail(ctx, CURVIS_E_INVALID, "the disc motion is Keplerian and needs the Schwarzschild metric: in the other kinds g00 = -1, free matter is at rest and nothing orbits (set the motion to 0: curvis_ctx_set_disc_motion)");
   }
   if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->sky_mipmap && !ctx->projection && !ctx->step_scale && !ctx->integrator)) return render_rays(ctx, c);
   /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under

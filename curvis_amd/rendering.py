@@ -115,16 +115,18 @@ def render_image_sharded(context, metric, camera, max_iterations, max_radius, de
     return np.concatenate([p[1] for p in parts], axis=0), [p[0] for p in parts]
 
 
-def check_disc_mode(disc, mode):
+def check_disc_mode(disc, mode, metric=None):
     """an accretion disc (curvis_amd.Disc) lives in the per-pixel renderer alone: ValueError for anything but a Disc or None, and for a
-    Disc with a mode other than "brute" -- there is no silent change of mode"""
-    from .systems import Disc
+    Disc with a mode other than "brute" -- there is no silent change of mode; and for a Disc with a motion under a metric that is not
+    a SchwarzschildMetric (systems.check_disc_metric)"""
+    from .systems import Disc, check_disc_metric
     if disc is None:
         return
     if not isinstance(disc, Disc):
         raise ValueError("disc must be a curvis_amd.Disc or None")
     if mode != "brute":
         raise ValueError("a disc needs mode='brute': mode=%r reduces every ray to an equatorial orbit and cannot see it" % (mode,))
+    check_disc_metric(disc, metric)
 
 
 class ImageRenderingSettings:
@@ -156,7 +158,7 @@ class ImageRenderingSystem:
                  projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
         from .images import load_image_as_spherical_image
         from .systems import RelativisticSystem, check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
-        check_disc_mode(disc, mode)
+        check_disc_mode(disc, mode, metric)
         check_step_scale(step_scale)
         self.step_scale = step_scale
         check_integrator(integrator)
@@ -245,7 +247,7 @@ class VideoRenderingSystem:
                  mode="efficient", sampling_initial_nums=100, sampling_convergence_threshold_1=1e-5, supersample=1,
                  sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
         from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
-        check_disc_mode(disc, mode)
+        check_disc_mode(disc, mode, metric)
         self.disc = disc
         self._step_scale = check_step_scale(step_scale)
         self.step_scale = step_scale
@@ -285,7 +287,7 @@ class VideoRenderingSystem:
         from .images import load_image_as_spherical_image
         from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context, SchwarzschildMetric, black_sky
         check_supersample(supersample)  # before the context and the files are touched
-        check_disc_mode(disc, mode)
+        check_disc_mode(disc, mode, metric)
         check_sky_mipmap(sky_mipmap)
         check_step_scale(step_scale)
         check_integrator(integrator)

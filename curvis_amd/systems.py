@@ -327,9 +327,20 @@ class Disc:
     """An accretion disc (not in the reference; include/curvis_hip.h has the definition): a thin annulus in the equatorial plane
     between the radial coordinates l_inner < l_outer (in l, of either sign: a negative value lies on the far side of a wormhole),
     textured with `image`, HxWx4 (RGBA8) or HxWx3 (RGB8, alpha := 255) -- W along azimuth, H along l.  Opaque where alpha >= 128,
-    absent elsewhere; it emits its texel's colour.  The ValueErrors are the refusals of curvis_ctx_set_disc."""
+    absent elsewhere; it emits its texel's colour.  motion="static" (the default) leaves it at that; "prograde" / "retrograde" put
+    the disc's matter on circular geodesics of Schwarzschild in the +phi / -phi direction, and the colour is scaled by
+    gain * g^4, g the frequency ratio between the emitting matter and the static camera (Doppler shift, beaming and gravitational
+    redshift; a SchwarzschildMetric only).  The ValueErrors are the refusals of curvis_ctx_set_disc and curvis_ctx_set_disc_motion."""
 
-    def __init__(self, image, l_inner, l_outer):
+    MOTIONS = {"static": 0, "prograde": 1, "retrograde": -1}
+
+    def __init__(self, image, l_inner, l_outer, motion="static", gain=1.0):
+        if not isinstance(motion, str) or motion not in self.MOTIONS:
+            raise ValueError("disc: motion must be 'static', 'prograde' or 'retrograde'")
+        if isinstance(gain, bool) or not isinstance(gain, (int, float, np.integer, np.floating)) or not np.isfinite(float(gain)) \
+                or float(gain) < 0.0:
+            raise ValueError("disc: the gain must be a finite number and not negative")
+        self.motion, self.gain = motion, float(gain)
         img = np.asarray(image)
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
             raise ValueError("image must be HxWx3 or HxWx4 uint8")
@@ -345,6 +356,13 @@ class Disc:
         self.rgba = np.ascontiguousarray(img)
         self.height_pixels, self.width_pixels = self.rgba.shape[:2]
         self.l_inner, self.l_outer = float(l_inner), float(l_outer)
+
+
+def check_disc_metric(disc, metric):
+    """a Disc with a motion is Keplerian: ValueError unless the metric is a SchwarzschildMetric (the library's refusal, made early)"""
+    if disc is not None and disc.motion != "static" and not isinstance(metric, SchwarzschildMetric):
+        raise ValueError("disc: motion=%r is Keplerian and needs a SchwarzschildMetric -- in the other metrics free matter is at "
+                         "rest and nothing orbits" % (disc.motion,))
 
 
 class HostBuffer:
@@ -415,15 +433,29 @@ class Context:
 
     def set_disc(self, disc):
         """curvis_ctx_set_disc: the context's accretion disc (a Disc), or None to remove it.  While one is set the brute renderer
-        honours it and the efficient renderer, the direct renderer and the debug dump refuse to render."""
+        honours it and the efficient renderer, the direct renderer and the debug dump refuse to render.  The disc's motion and gain
+        are set with it (curvis_ctx_set_disc_motion; None puts them back to static and 1)."""
         if disc is None:
             check(lib().curvis_ctx_set_disc(self._h, None, 0, 0, 0.0, 0.0), self._h)
+            self.set_disc_motion("static", 1.0)
         else:
             if not isinstance(disc, Disc):
                 raise ValueError("disc must be a curvis_amd.Disc or None")
             check(lib().curvis_ctx_set_disc(self._h, disc.rgba.ctypes.data, disc.width_pixels, disc.height_pixels, disc.l_inner,
                                             disc.l_outer), self._h)
+            self.set_disc_motion(disc.motion, disc.gain)
         self._disc_obj = disc
+
+    def set_disc_motion(self, motion, gain=1.0):
+        """curvis_ctx_set_disc_motion: "static", "prograde" or "retrograde" (or the ABI's 0, 1, -1) and the gain; ValueError for
+        its refusals"""
+        sigma = Disc.MOTIONS.get(motion, motion) if isinstance(motion, str) else motion
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, np.integer)) or int(sigma) not in (-1, 0, 1):
+            raise ValueError("disc: motion must be 'static', 'prograde' or 'retrograde'")
+        try:
+            check(lib().curvis_ctx_set_disc_motion(self._h, int(sigma), float(gain)), self._h)
+        except _abi.CurvisError as e:
+            raise ValueError(str(e)) from None
 
     def frame_disc_hits(self, frame=None):
         """rays that ended on the disc in one frame (or the list for all frames) of the last render call (curvis_ctx_frame_disc_hits)"""
@@ -966,6 +998,7 @@ class RelativisticSystem:
     def __init__(self, metric, background_positive, background_negative, camera, context=None, disc=None):
         if disc is not None and not isinstance(disc, Disc):
             raise ValueError("disc must be a curvis_amd.Disc or None")
+        check_disc_metric(disc, metric)
         self.disc = disc
         self.metric = metric
         self.background_positive = background_positive

@@ -59,7 +59,9 @@ enum { CURVIS_METRIC_ELLIS = 0, CURVIS_METRIC_INTERSTELLAR = 1, CURVIS_METRIC_FL
  * escapes to -l, so the escape test, the which-side code and the counters (n_neg = captured rays) are the ones every kind has, and the
  * sky set for -l is "what is painted on the horizon" -- set an opaque black one and the shadow appears.  What is represented: the null
  * geodesics and the local angles of Schwarzschild, for a camera that is a static observer at areal radius r(l_camera).  What is not:
- * proper time and redshift (curvis_metric_functions and curvis_metric_tensor return the optical metric, whose g00 is -1).
+ * proper time and redshift (curvis_metric_functions and curvis_metric_tensor return the optical metric, whose g00 is -1) -- the
+ * one exception is the emission of a moving accretion disc (curvis_ctx_set_disc_motion), which is scaled by the physical metric's
+ * frequency ratio.
  *
  * Definition of R, R^2 and R' at l -- an explicit sequence of individually rounded FP64 operations, one text for host and device
  * (cv_device.h metric_eval, cv_math.h cv_tortoise_u), a pure function of l: no iteration count that depends on the data, nothing
@@ -194,7 +196,8 @@ int curvis_ctx_sky_mip_level(curvis_ctx *ctx, int which, uint32_t level, uint8_t
  * doubles l_inner < l_outer of either sign.  The bounds are in the radial coordinate l, not in r(l): l is monotonic in every metric
  * kind (the Schwarzschild kind's R(l) is not), and negative values put the disc on the far side of a wormhole.  The disc lies in the
  * plane theta = pi/2 (mod pi), is infinitely thin, opaque where its texel's alpha is >= 128 and absent where it is < 128, and emits its
- * texel's colour: no redshift, no Doppler shift, no beaming (see what the Schwarzschild paragraph says is not represented).
+ * texel's colour: no redshift, no Doppler shift, no beaming (see what the Schwarzschild paragraph says is not represented) -- unless
+ * the disc is given a motion, curvis_ctx_set_disc_motion below.
  *
  * Notation for a ray.  y_0 is the photon at the camera, y_k the state after k steps of whatever the call's step is (the Euler step,
  * "step_scale"'s step, or a Heun step; the stage states of a Heun step are not states).  (s_k, c_k) is the one cv_math.h sincos
@@ -231,7 +234,55 @@ int curvis_ctx_sky_mip_level(curvis_ctx *ctx, int which, uint32_t level, uint8_t
  * curvis_compute_escape_angles and curvis_walk_ray do not see it.  With no disc set every call launches exactly the kernels it
  * launched before there was one. */
 int curvis_ctx_set_disc(curvis_ctx *ctx, const uint8_t *rgba, uint32_t w, uint32_t h, double l_inner, double l_outer);
-/* Steps 1-7 above for one pair of consecutive states, on the host (no GPU needed): *hit = 1 when the ray crossed the plane inside
+/* The disc's emission shift (not in the reference): the disc gets a motion sigma in {0, +1, -1} and a gain G.  sigma = 0 is the disc of
+ * the paragraph above, bit for bit, and G is not applied.  With sigma = +-1 the disc's matter moves on circular geodesics of
+ * Schwarzschild in the +-phi direction, Omega = sigma sqrt(M / r^3), and the camera is the static observer the project assumes
+ * everywhere.  A ray is traced with covariant momentum p_t = 1 and constant p_phi (its angular momentum about the disc's axis: the disc
+ * lies in the coordinate equator); covariant components are conformally invariant, so the optical-metric ray carries the p_t, p_phi of
+ * the physical one.  The frequency ratio of a ray that ends on the disc at l_hit (r_e there, r_c at the camera; the sign of the
+ * past-directed tracing cancels in the ratio) is
+ *   g = sqrt(1 - 3M/r_e) / (sqrt(1 - 2M/r_c) (1 + Omega p_phi)),
+ * and the emitted colour is scaled by the bolometric factor F = G g^4: Doppler shift, beaming and gravitational redshift in one
+ * number, no change of hue.  In the kind's own variable u = r/2M - 1 that is one square root and no fourth root.  F is DEFINED as this
+ * sequence, every operation individually rounded, no fma:
+ *   1. u_e = schwarzschild_u(M, l_hit) and u_c = schwarzschild_u(M, l_camera): the kind's function (curvis_schwarzschild_u), its
+ *      l < 0 funnel included.  l_camera is the frame's camera coordinate, l_hit the value of step 3 above.
+ *   2. w = 1 + u_e and n = 2 u_e - 1.  If !(n > 0): F = 0 -- at or inside the photon sphere r = 3M, where there is no circular orbit;
+ *      the ray still ends on the disc, and is painted black.
+ *   3. a = n / (2 w).  This is 1 - 3M/r_e.
+ *   4. om = RN(1/2M) / (w sqrt(2 w)).  This is |Omega|; RN(1/2M) is the constant the kind already carries.
+ *   5. den = 1 + (sigma om) p_phi.  If !(den > 0): F = 0.  In exact arithmetic |Omega p_phi| < 1 outside r = 3M: the null condition
+ *      of the optical metric, p_l^2 + (p_theta^2 + p_phi^2 / sin^2 theta) / R^2 = 1, gives |p_phi| <= R(r) in the equator, and
+ *      Omega R = sqrt(M / r^3) r / sqrt(1 - 2M/r) = sqrt(M / (r - 2M)), which is below 1 exactly when r > 3M.  The test keeps a
+ *      caller's oversized p_phi (curvis_disc_shift takes any) and the roundings next to r = 3M from a negative or infinite g.
+ *   6. A_c = u_c / (1 + u_c).  This is 1 - 2M/r_c.
+ *   7. g2 = a / (A_c (den den)).
+ *   8. F = G (g2 g2).
+ * The quotients are the correctly rounded ones, the root is IEEE's.  Colour: for each of the three 8-bit channels c of the texel,
+ * v = (double)c F + 0.5 and c' = (v >= 255.0) ? 255 : as_u32(v) (`as u32`: truncation, NaN and negatives to 0; a NaN cannot occur after
+ * steps 2 and 5 for a ray the renderer traced).  Alpha is kept, so "non-zero texel = ended on the disc" still holds.  The shifted colour
+ * replaces the texel's colour everywhere the paragraph above speaks of it: in the "supersample" average, in the "sky_filter" and
+ * "sky_mipmap" branches that take the disc ray's own colour, in row bands and in batches (each frame with its own camera's u_c).
+ * Codes, step counts and every counter, n_disc included, are those of sigma = 0.  Steps 1-8 are one function for host and device
+ * (cv_device.h disc_shift, the colour disc_shade); curvis_disc_shift and curvis_disc_shade are the host accessors.
+ *
+ * curvis_ctx_set_disc_motion: motion = sigma, gain = G; the default is (0, 1.0).  CURVIS_E_INVALID for a motion outside {-1, 0, 1} or a
+ * gain that is not finite or is negative; the former values then stay.  The setting belongs to the context, survives
+ * curvis_ctx_set_disc (also the removal of the disc) and does nothing without a disc.  A brute render call (curvis_render_brute, _rows,
+ * _batch) with a disc, motion != 0 and a metric kind other than CURVIS_METRIC_SCHWARZSCHILD is refused with CURVIS_E_INVALID and a
+ * message that names the disc motion: the wormhole kinds and flat space have g_00 = -1, free matter there is at rest, and nothing is
+ * Keplerian.  Every refusal of the paragraph above stays.  With motion = 0 every call launches exactly the kernels it launched before
+ * there was a motion. */
+int curvis_ctx_set_disc_motion(curvis_ctx *ctx, int motion, double gain);
+/* Steps 1-8 above on the host (no GPU needed): *F for a Schwarzschild metric `m`, the crossing's l_hit, the camera's l, motion (+-1;
+ * 0 gives *F = gain's neutral value 1.0: the colour is the texel's), gain and the ray's p_phi, all taken as they are.
+ * CURVIS_E_INVALID for a null pointer, a metric that is not of kind CURVIS_METRIC_SCHWARZSCHILD, or a motion outside {-1, 0, 1};
+ * CURVIS_E_METRIC for a metric curvis_metric_validate refuses. */
+int curvis_disc_shift(const curvis_metric *m, double l_hit, double l_camera, int motion, double gain, double p_phi, double *F);
+/* The colour rule above for one RGBA8 texel (red in the low byte): *out = the texel with its three colour channels scaled by F, alpha
+ * kept.  CURVIS_E_INVALID for a null pointer. */
+int curvis_disc_shade(uint32_t texel, double F, uint32_t *out);
+/* Steps 1-7 of the disc's paragraph for one pair of consecutive states, on the host (no GPU needed): *hit = 1 when the ray crossed the plane inside
  * [l_inner, l_outer], and then (*tx, *ty) is the texel; *hit = 0 otherwise (tx, ty = 0).  The alpha test of step 8 is the caller's.
  * CURVIS_E_INVALID for a null pointer, w == 0 or h == 0; the bounds are taken as they are. */
 int curvis_disc_crossing(double c_prev, double c_cur, double s_cur, double l_prev, double l_cur, double phi_prev, double phi_cur,
