@@ -1,6 +1,6 @@
 """The disc's emission shift (include/curvis_hip.h, the paragraph after the disc's): the definition in Python doubles, written from that
-text, and the brute renderer's frame with a moving disc composed per ray over disc_ref.  Step 1 is the library's pre-existing host
-accessor curvis_schwarzschild_u; everything else is one Python operation per operation of the header:
+text, and the brute renderer's frame with a moving disc composed per ray over disc_ref, whose probe hands out l_hit and p_phi.  Step 1
+is the library's pre-existing host accessor curvis_schwarzschild_u; everything else is one Python operation per operation of the header:
 
   w = 1 + u_e;  n = 2 u_e - 1;            !(n > 0): F = 0
   a = n / (2 w)
@@ -20,14 +20,11 @@ import numpy as np
 import disc_ref as D
 import oracle_lib as O
 import projection_ref as P
+import ref_compose as RC
 import step_scale_ref as SR
 
 STATIC, PROGRADE, RETROGRADE = 0, 1, -1
-
-
-def _div(n, d):
-    with np.errstate(all="ignore"):
-        return float(np.float64(n) / np.float64(d))
+_div = RC._div
 
 
 def _sqrt(x):
@@ -92,68 +89,6 @@ def shade_rgb(rgb, F):
     return [shade_channel(int(c), F) for c in rgb]
 
 
-class Walk(D.Walk):
-    """disc_ref.Walk.run with l_hit (steps 2-3 of the disc's paragraph) and p_phi handed out for a ray that ends on the disc"""
-
-    def run(self, disc, delta, S, integrator, max_iter, max_radius):
-        """(code, steps, (tx, ty) or None, l_hit, p_phi)"""
-        cx = self.cx
-        assert abs(cx[1]) <= max_radius
-        kap = SR.kappa(delta, S) if S else 0.0
-        code, steps = O.NOT_ESCAPED, 0
-        c_prev = l_prev = ph_prev = 0.0
-        while steps < max_iter:
-            l, ph = cx[1], cx[3]
-            s, c = self.sincos(cx[2])
-            if steps >= 1:
-                hit = D.crossing(c_prev, c, s, l_prev, l, ph_prev, ph, disc.l_in, disc.l_out, disc.w, disc.h)
-                if hit is not None and disc.alpha[hit[1]][hit[0]] >= 128:
-                    t = _div(c_prev, c_prev - c)
-                    l_hit = l_prev + t * (l - l_prev)
-                    return D.DISC, steps, hit, l_hit, self.cp[3]
-            c_prev, l_prev, ph_prev = c, l, ph
-            dk = delta
-            if S:
-                a = abs(l) * kap
-                if a > delta:
-                    dk = a
-            if integrator:
-                self.heun(dk)
-            else:
-                self.st.euler(dk)
-            steps += 1
-            if cx[1] > max_radius:
-                code = O.POSITIVE
-                break
-            if cx[1] < -max_radius:
-                code = O.NEGATIVE
-                break
-        return code, steps, None, 0.0, self.cp[3]
-
-
-def walk_rays(stepper, cam_pos, dirs, disc, max_iter, max_radius, delta, S=0, integrator=0):
-    """disc_ref.walk_rays' per-ray arrays (those the frame composers read) plus l_hit and p_phi"""
-    H, W = dirs.shape[:2]
-    r = dict(code=np.zeros((H, W), np.int64), steps=np.zeros((H, W), np.int64), d=np.zeros((H, W, 3)), texel=np.zeros((H, W, 2), np.int64),
-             l_hit=np.zeros((H, W)), p_phi=np.zeros((H, W)))
-    pos = np.array(cam_pos[:], dtype=np.float64)
-    w = Walk(stepper)
-    d = np.zeros(3)
-    for j in range(H):
-        for i in range(W):
-            stepper.new_photon(pos, dirs[j, i])
-            code, steps, hit, l_hit, p_phi = w.run(disc, delta, S, integrator, max_iter, max_radius)
-            r["code"][j, i], r["steps"][j, i], r["l_hit"][j, i], r["p_phi"][j, i] = code, steps, l_hit, p_phi
-            if code == D.DISC:
-                r["texel"][j, i] = hit
-            elif code != O.NOT_ESCAPED:
-                stepper.direction(d)
-                r["d"][j, i] = d
-    for v in r.values():
-        v.setflags(write=False)
-    return r
-
-
 # ---- the scenes: disc_ref's Schwarzschild scene (SCHW_*, CAP, R, DELTA), walked once per shape and shaded per motion and gain --------
 R, DELTA, CAP = D.R, D.DELTA, D.CAP
 _cache = {}
@@ -176,7 +111,7 @@ def scene_rays(l_cam=D.SCHW_L_CAM, l_inner=None, res=D.SCHW_RES, S=0, integrator
     key = ("rays", l_cam, l_inner, res, S, integrator, projection)
     if key not in _cache:
         pm, oc, _, dsc = scene(l_cam, l_inner, res)
-        _cache[key] = walk_rays(D.HostStepper(pm), oc.pos, SR.world_dirs(oc, projection), dsc, CAP, R, DELTA, S, integrator)
+        _cache[key] = D.walk_rays(D.HostStepper(pm), oc.pos, SR.world_dirs(oc, projection), dsc, CAP, R, DELTA, S, integrator, motion=True)
     return _cache[key]
 
 
@@ -198,12 +133,7 @@ def scene_frame(sigma, gain=1.0, lookup="nearest", l_cam=D.SCHW_L_CAM, l_inner=N
     if key not in _cache:
         rays = scene_rays(l_cam, l_inner, **kw)
         dsc = scene(l_cam, l_inner)[3]
-        if lookup == "nearest":
-            rgb, cnt = D.frame_nearest(rays, dsc, SR.oracle_skies())
-        elif lookup == "bilinear":
-            rgb, cnt = D.frame_bilinear(rays, dsc, SR.index_skies())
-        else:
-            rgb, cnt = D.frame_mipmap(rays, dsc, SR.index_skies())
+        rgb, cnt = RC.frame(rays, dsc, lookup, SR.index_skies(), SR.oracle_skies())
         rgb = np.array(rgb)
         F = factors(rays, l_cam, sigma, gain) if sigma else np.zeros(rays["code"].shape)
         if sigma:

@@ -9,11 +9,10 @@ The vocabulary and the grids are tests/kernel_matrix_ref.py's, unchanged; so are
 camera positions of the other two, whose cameras are turned towards the throat (MOVED says why).  The enumeration is written from with_launch_shape
 (curvis_amd/csrc/render_host.h) and from the launches in curvis_amd/csrc/efficient_host.h; nothing of it is read from the product.
 
-The reference composes what exists: ONE equatorial escape-angle evaluator (a photon at (0, l_cam, pi/2, 0) along (cos a, 0, sin a), walked
-by disc_ref.Walk over disc_ref.stepper_of's stepper under the step option and the integrator, no disc, then the angle as
-step_scale_ref.EscapeAngle and schwarzschild_ref.compute_escape_angle form it), projection_ref's pixel geometry and final direction,
-ref_python.doubly_sample_function for the sample table, the oracle's interp_slice for the interpolation, disc_ref's three lookups over a
-{code, steps, d} array and step_scale_ref.box_average.  Every walk, table and fine frame is computed once, shared and read-only.  No GPU."""
+The reference composes what tests/ref_compose.py holds: its equatorial escape-angle evaluator over the kind's stepper under the step
+option and the integrator, an alpha walked once; its direct and efficient compositions over projection_ref's pixel geometry; its sample
+table; its three lookups over a {code, steps, d} array; and box_average.  Every walk, table and fine frame is computed once, shared and
+read-only.  No GPU."""
 import math
 
 import numpy as np
@@ -21,25 +20,19 @@ import numpy as np
 import disc_ref as D
 import oracle_lib as O
 import projection_ref as P
-import ref_python
+import ref_compose as RC
 import step_scale_ref as SR
 import kernel_matrix_ref as K
 from kernel_matrix_ref import (KINDS, STEPS, SUPERSAMPLES, LOOKUPS, PROJECTIONS, STEP_OPTIONS, STEP_WALKS, LOOKUP_OPTIONS, cell_options,  # noqa: F401
                                GRIDS, product_res, scene_parameters, R, DELTA, CAP)
 
 EFF = SR.EFF                                   # n0 = 100, maxit = 100, thresholds 1e-5
-A_MIN, A_MAX = -0.1 * np.pi, 1.1 * np.pi       # src/systems.rs:437-438
+A_MIN, A_MAX = RC.A_MIN, RC.A_MAX
 # scaled Heun steps: the walk of "everything at once" -- not one of the four step forms, both options of the ADAPT = 2 kernels at once
 EVERYTHING = "everything"
 WALKS = dict(STEP_WALKS, everything=(K.STEP_SCALE, 1))
 WALK_OPTIONS = dict(STEP_OPTIONS, everything=dict(step_scale=K.STEP_SCALE, integrator=1))
-_cache = {}
-
-
-def memo(key, make):
-    if key not in _cache:
-        _cache[key] = make()
-    return _cache[key]
+memo = RC.memo
 
 
 # ---- the enumerations ------------------------------------------------------------------------------------------------------------------
@@ -73,51 +66,6 @@ HOST_PACED_FORMS = ((1, "nearest", "perspective", 0), (1, "nearest", "fisheye", 
 
 
 # ---- the equatorial escape-angle evaluator -----------------------------------------------------------------------------------------------
-class EscapeAngle:
-    """compute_escape_angle (src/systems.rs:203-261) for all four kinds under S and the integrator: (code, angle, steps), the angle NaN
-    where the photon did not escape, code O.PANIC where the reference panics (the tangent rotation is undefined).  An alpha is walked
-    once; calls and steps count every call, as the reference's closure would."""
-
-    def __init__(self, om, pm, l, S, integrator, cap=CAP, max_radius=R, delta=DELTA):
-        self.st = D.stepper_of(om, pm)
-        self.walk = D.Walk(self.st)
-        self.l, self.S, self.integrator, self.cap, self.max_radius, self.delta = float(l), S, integrator, cap, max_radius, delta
-        self.calls = self.steps = 0
-        self.seen = {}
-
-    def _eval(self, alpha):
-        L, st = O.lib(), self.st
-        a1 = np.array([alpha], dtype=np.float64)
-        sa, ca = float(O.math_array(O.CV, 0, a1)[0]), float(O.math_array(O.CV, 1, a1)[0])
-        st.new_photon(np.array([0.0, self.l, np.pi / 2.0, 0.0]), np.array([ca, 0.0, sa]))
-        code, steps = self.walk.run(None, self.delta, self.S, self.integrator, self.cap, self.max_radius)[:2]
-        if code == O.NOT_ESCAPED:
-            return code, float("nan"), steps
-        tdir, wpos, rot, wd = np.zeros(3), np.zeros(3), np.zeros(9), np.zeros(3)
-        st.direction(tdir)
-        L.cvo_vector3_from_theta_phi(O.CV, float(st.x[2]), float(st.x[3]), O._dp(wpos))
-        if L.cvo_rotation_from_two_vectors(O.CV, O._dp(np.array([1.0, 0.0, 0.0])), O._dp(wpos), O._dp(rot)) != 0:
-            return O.PANIC, float("nan"), steps
-        L.cvo_mat3_vec(O._dp(rot), O._dp(tdir), O._dp(wd))
-        x, y, z = float(wd[0]), float(wd[1]), float(wd[2])
-        n = math.sqrt(x * x + y * y + z * z)
-        x, y, z = x / n, y / n, z / n
-        vx = x * 1.0 + y * 0.0 + z * 0.0
-        vy = x * 0.0 + y * 1.0 + z * 0.0
-        acos = float(O.math_array(O.CV, 3, np.array([vx]))[0])
-        return code, (acos if vy >= 0.0 else 2.0 * np.pi - acos), steps
-
-    def __call__(self, alpha):
-        alpha = float(alpha)
-        key = alpha.hex()
-        if key not in self.seen:
-            self.seen[key] = self._eval(alpha)
-        out = self.seen[key]
-        self.calls += 1
-        self.steps += out[2]
-        return out
-
-
 def metrics_of(kind):
     """(oracle metric or None, product metric): disc_ref.scene_from's"""
     sc = K.scene(kind, GRIDS[1])
@@ -146,7 +94,8 @@ def evaluator(kind, step, l=None, cap=CAP):
     """the one evaluator of (kind, step walk, camera radius, cap)"""
     S, integrator = WALKS[step]
     l = camera_radius(kind) if l is None else float(l)
-    return memo(("evaluator", kind, S, integrator, l, cap), lambda: EscapeAngle(*metrics_of(kind), l, S, integrator, cap))
+    return memo(("evaluator", kind, S, integrator, l, cap),
+                lambda: RC.EscapeAngle(RC.stepper_of(*metrics_of(kind)), l, DELTA, S, integrator, cap, R, memo=True))
 
 
 # ---- cameras and geometry ---------------------------------------------------------------------------------------------------------------
@@ -181,37 +130,13 @@ def optical_axis_pixels(kind, projection, grid, pose=None):
     return int(on_axis.sum()), int((on_axis & nan_axis).sum())
 
 
-def _final(axis, angle, cam_bg):
-    with np.errstate(all="ignore"):
-        return P._final_direction(axis, angle, cam_bg)
-
-
-def _frozen(r):
-    for v in r.values():
-        v.setflags(write=False)
-    return r
-
-
 # ---- the direct renderer -----------------------------------------------------------------------------------------------------------------
 def _direct_rays(kind, step, projection, grid, cap=CAP, pose=None):
     S, integrator = WALKS[step]
     l = camera_radius(kind) if pose is None else float(pose[0][1])
 
     def make():
-        alphas, axes, cam_bg, _ = geometry(kind, projection, grid, pose)
-        f = evaluator(kind, step, l, cap)
-        H, W = alphas.shape
-        r = dict(code=np.zeros((H, W), np.int64), steps=np.zeros((H, W), np.int64), d=np.zeros((H, W, 3)))
-        for j in range(H):
-            for i in range(W):
-                code, ang, steps = f(alphas[j, i])
-                r["steps"][j, i] = steps
-                if code in (O.POSITIVE, O.NEGATIVE):      # (a panic of the reference is a black pixel of the direct mode)
-                    r["code"][j, i] = code
-                    r["d"][j, i] = _final(axes[j, i], ang, cam_bg)
-                else:
-                    r["code"][j, i] = O.NOT_ESCAPED
-        return _frozen(r)
+        return RC.compose_direct(evaluator(kind, step, l, cap), None, None, geometry(kind, projection, grid, pose))
     return memo(("direct rays", kind, S, integrator, projection, grid, cap, pose), make)
 
 
@@ -224,11 +149,8 @@ def direct_rays(kind, step, projection, grid):
 def compose(rays, lookup, steps=None):
     """(frame, (rays, steps, n_pos, n_neg, n_none, n_oob)) of a {code, steps, d} array under a lookup; steps: the sampler's, in place of
     the rays' sum"""
-    rgb, cnt = K.compose(rays, None, lookup)
-    cnt = cnt[:6]
-    if steps is not None:
-        cnt = (cnt[0], int(steps)) + cnt[2:]
-    return rgb, cnt
+    rgb, cnt = RC.frame(rays, None, lookup, SR.index_skies(), SR.oracle_skies(), steps)
+    return rgb, cnt[:6]
 
 
 def _resolve(fine, supersample):
@@ -269,16 +191,8 @@ def table(kind, step, l=None, cap=CAP, thr=TIGHT):
     def run(f, maxit):
         calls, steps = f.calls, f.steps
 
-        def closure(alpha):
-            code, ang, _ = f(alpha)
-            assert code != O.PANIC, (kind, step, l, alpha)
-            if code == O.POSITIVE:
-                return ang, 1.0
-            if code == O.NEGATIVE:
-                return ang, -1.0
-            return float("nan"), float("nan")
-        a, e, s = ref_python.doubly_sample_function(A_MIN, A_MAX, EFF["n0"], maxit, thr[0], thr[1], closure)
-        return (a, e, s), f.calls - calls, f.steps - steps
+        a, e, s = RC.sample_table(f, EFF["n0"], maxit, thr[0], thr[1])
+        return (a.tolist(), e.tolist(), s.tolist()), f.calls - calls, f.steps - steps
 
     def make():
         f = evaluator(kind, step, l, cap)
@@ -288,7 +202,7 @@ def table(kind, step, l=None, cap=CAP, thr=TIGHT):
         warned = int(rounds == EFF["maxit"] and run(f, EFF["maxit"] + 1)[:2] != full[:2])
         (a, e, s), calls, steps = full
         t = dict(a=np.array(a, dtype=np.float64), e=np.array(e, dtype=np.float64), s=np.array(s, dtype=np.float64))
-        _frozen(t)
+        RC.frozen(t)
         t.update(n=len(a), calls=calls, steps=steps, rounds=rounds, warned=warned, peak=peak)
         return t
     return memo(("table", kind, S, integrator, l, cap, thr), make)
@@ -374,24 +288,8 @@ def _efficient_rays(kind, step, projection, grid, pose=None, thr=TIGHT):
     l = camera_radius(kind) if pose is None else float(pose[0][1])
 
     def make():
-        alphas, axes, cam_bg, _ = geometry(kind, projection, grid, pose)
         t = table(kind, step, l, thr=thr)
-        H, W = alphas.shape
-        flat = np.ascontiguousarray(alphas.reshape(-1))
-        esc, spc = np.zeros(flat.size), np.zeros(flat.size)
-        O.lib().cvo_interp_slice(O._dp(t["a"]), O._dp(t["e"]), t["n"], O._dp(flat), flat.size, O._dp(esc))
-        O.lib().cvo_interp_slice(O._dp(t["a"]), O._dp(t["s"]), t["n"], O._dp(flat), flat.size, O._dp(spc))
-        esc, spc = esc.reshape(H, W), spc.reshape(H, W)
-        r = dict(code=np.zeros((H, W), np.int64), steps=np.zeros((H, W), np.int64), d=np.zeros((H, W, 3)))
-        for j in range(H):
-            for i in range(W):
-                v = spc[j, i]
-                if v == 1.0 or v == -1.0:
-                    r["code"][j, i] = O.POSITIVE if v == 1.0 else O.NEGATIVE
-                    r["d"][j, i] = _final(axes[j, i], esc[j, i], cam_bg)
-                else:
-                    r["code"][j, i] = O.NOT_ESCAPED
-        return _frozen(r)
+        return RC.compose_efficient((t["a"], t["e"], t["s"]), None, None, geometry(kind, projection, grid, pose))
     return memo(("efficient rays", kind, S, integrator, projection, grid, pose, thr), make)
 
 

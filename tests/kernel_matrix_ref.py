@@ -3,9 +3,9 @@ projection, 384 cells, each once plain and once as a DISC form -- and the 96 for
 counters of every cell.  The enumeration is written from the static asserts of geodesic_static and from launch_disc / launch_integrate
 (curvis_amd/csrc/render_host.h); nothing of it is read from the product.
 
-The reference is tests/disc_ref.py's, which is compositional: a ray is walked by the oracle's own step (the library's host accessors for
-the Schwarzschild kind) under the step option, and the lookup and the supersampling are pure functions of a walked fine grid.  So the
-twelve cells of one (kind, step walk, projection) share two walks, one per fine grid:
+The reference is tests/disc_ref.py's over tests/ref_compose.py, which is compositional: a ray is walked by the oracle's own step (the
+library's host accessors for the Schwarzschild kind) under the step option, and the lookup and the supersampling are pure functions of a
+walked fine grid.  So the twelve cells of one (kind, step walk, projection) share two walks, one per fine grid:
 
   20 x 12  supersample 1, 2 and 4: ragged 8 x 8 tiles in both directions; frames of 20 x 12, 10 x 6 and 5 x 3
   16 x  8  supersample 8: a frame of 2 x 1 (a fine grid of 8 N can never be ragged)
@@ -18,6 +18,7 @@ import numpy as np
 import disc_ref as D
 import oracle_lib as O
 import projection_ref as P
+import ref_compose as RC
 import step_scale_ref as SR
 
 KINDS = ("ellis", "interstellar", "flat", "schwarzschild")
@@ -115,14 +116,7 @@ def walk(kind, step, projection, grid, disc):
 
 def compose(rays, dsc, lookup):
     """(frame, counters) of walked rays under a lookup; dsc None: the plain kernel's frame"""
-    if lookup == "nearest":
-        out = D.frame_nearest(rays, dsc, SR.oracle_skies())
-    elif lookup == "bilinear":
-        out = D.frame_bilinear(rays, dsc, SR.index_skies())
-    else:
-        out = D.frame_mipmap(rays, dsc, SR.index_skies())
-    out[0].setflags(write=False)
-    return out
+    return RC.frame(rays, dsc, lookup, SR.index_skies(), SR.oracle_skies())
 
 
 def fine_frame(kind, step, projection, grid, lookup, disc):
@@ -224,7 +218,7 @@ def first_iteration_hit():
     """the opaque texel a plane test of the first iteration would find against a previous state of zeros, or None"""
     sc = below_scene()
     pos, dsc = sc[3].pos, sc[5]
-    s0, c0 = D.Walk(D.stepper_of(sc[1], sc[2])).sincos(pos[2])
+    s0, c0 = RC.Walk(D.stepper_of(sc[1], sc[2])).sincos(pos[2])
     hit = D.crossing(0.0, c0, s0, 0.0, pos[1], 0.0, pos[3], dsc.l_in, dsc.l_out, dsc.w, dsc.h)
     return hit if hit is not None and dsc.alpha[hit[1]][hit[0]] >= 128 else None
 

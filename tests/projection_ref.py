@@ -250,11 +250,8 @@ def scene(kind, res, focal=FOCAL, l=POS[1]):
 
 
 def index_skies():
-    if "skies" not in _cache:
-        _cache["skies"] = tuple(common.index_sky(w, h, s) for (w, h), s in zip(SKY_SHAPES, SKY_SALTS))
-        for t in _cache["skies"]:
-            t.setflags(write=False)
-    return _cache["skies"]
+    import ref_compose      # (it imports this module)
+    return ref_compose.index_skies(SKY_SHAPES, SKY_SALTS)
 
 
 def efficient_args(cap=CAP):

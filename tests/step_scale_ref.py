@@ -1,6 +1,6 @@
 """Library option "step_scale" (an integer S; L0 = S / 256): the definition in Python doubles, written from the option's paragraph in
-include/curvis_hip.h, and each renderer's frame composed per ray from primitives of the CPU oracle that exist already.  Nothing here
-calls the product, and nothing is added to the oracle.
+include/curvis_hip.h, and each renderer's frame composed per ray by tests/ref_compose.py from primitives of the CPU oracle that exist
+already.  Nothing here calls the product, and nothing is added to the oracle.
 
   kappa   = RN(delta / L0)                       one IEEE division per call
   a       = RN(|l_k| kappa)                      l_k: the radial coordinate BEFORE step k
@@ -13,10 +13,9 @@ import math
 
 import numpy as np
 
-import common
 import oracle_lib as O
 import projection_ref as P
-import ref_python
+import ref_compose as RC
 
 COUNTERS = P.COUNTERS
 S_MAX = 1 << 20
@@ -34,194 +33,51 @@ def step_delta(delta, S, l, k=None):
     return a if a > delta else delta
 
 
-class Walk:
-    """one ray's loop: buffers and pointers made once, since a frame makes a few hundred thousand oracle calls"""
-
-    def __init__(self, metric):
-        self.metric = metric
-        self.mp = C.byref(metric)
-        self.x, self.p = np.zeros(4), np.zeros(4)
-        self.xp, self.pp = O._dp(self.x), O._dp(self.p)
-        self.update = O.lib().cvo_update
-
-    def run(self, delta, S, max_iter, max_radius, inner=None):
-        """escape_photon (src/systems.rs:115-139) on (self.x, self.p) in place with delta_k per step:
-        (code, steps, steps taken with delta_k == delta, steps taken from |l| < inner)"""
-        x, xp, pp, mp, update = self.x, self.xp, self.pp, self.mp, self.update
-        if abs(x[1]) > max_radius:
-            return O.PANIC, 0, 0, 0
-        k = kappa(delta, S) if S else 0.0
-        code, steps, plain, inside = O.NOT_ESCAPED, 0, 0, 0
-        while steps < max_iter:
-            l = float(x[1])
-            dk = delta
-            if S:
-                a = abs(l) * k
-                if a > delta:
-                    dk = a
-            plain += dk == delta
-            if inner is not None and abs(l) < inner:
-                inside += 1
-            update(O.CV, mp, xp, pp, dk)
-            steps += 1
-            if x[1] > max_radius:
-                code = O.POSITIVE
-                break
-            if x[1] < -max_radius:
-                code = O.NEGATIVE
-                break
-        return code, steps, plain, inside
-
-
 def strict_radius(metric):
     """Interstellar: the fast step's guard sends |l| < a + pi m to the strict step"""
     return metric.a + math.pi * metric.m if metric.kind == O.INTERSTELLAR else None
 
 
-def compose_brute(metric, cam, dirs, sky_pos, sky_neg, max_iter, max_radius, delta, S):
-    """RelativisticSystem::render_image over the world-space directions dirs [H, W, 3] with scaled steps:
-    (frame, counters, debug records [H, W] of O.RAY_DEBUG, classes) -- classes: per ray (plain steps, scaled steps, strict-zone steps)"""
-    L = O.lib()
-    H, W = dirs.shape[:2]
-    rgb = np.zeros((H, W, 3), np.uint8)
-    dbg = np.zeros((H, W), O.RAY_DEBUG)
-    classes = np.zeros((H, W, 3), np.int64)
-    cnt = dict.fromkeys(COUNTERS, 0)
-    pos = np.array(cam.pos[:])
-    d = np.zeros(3)
-    w = Walk(metric)
-    inner = strict_radius(metric)
+def evaluator(metric, l, delta, S, max_iter, max_radius, integrator=0):
+    """ref_compose's escape-angle evaluator over the oracle's stepper, counting the strict zone's steps"""
+    return RC.EscapeAngle(RC.OracleStepper(metric), l, delta, S, integrator, max_iter, max_radius, strict_radius(metric))
+
+
+def _texel_of(sky_pos, sky_neg):
     tx, ty = C.c_uint32(0), C.c_uint32(0)
-    for j in range(H):
-        for i in range(W):
-            L.cvo_new_photon(O.CV, w.mp, O._dp(pos), O._dp(np.ascontiguousarray(dirs[j, i])), w.xp, w.pp)
-            code, steps, plain, inside = w.run(delta, S, max_iter, max_radius, inner)
-            assert code != O.PANIC
-            r = dbg[j, i]
-            r["x"], r["p"], r["steps"], r["code"] = w.x, w.p, steps, code
-            classes[j, i] = (plain, steps - plain, inside)
-            cnt["rays"] += 1
-            cnt["steps"] += steps
-            if code in (O.POSITIVE, O.NEGATIVE):
-                sky = sky_pos if code == O.POSITIVE else sky_neg
-                L.cvo_vector_to_direction(O.CV, w.mp, w.pp, w.xp, O._dp(d))
-                L.cvo_sky_indices(O.CV, C.byref(sky), O._dp(d), C.byref(tx), C.byref(ty))
-                r["tx"], r["ty"] = tx.value, ty.value
-                cnt["n_oob"] += P._shade(sky, d, rgb[j, i])
-                cnt["n_pos" if code == O.POSITIVE else "n_neg"] += 1
-            else:
-                cnt["n_none"] += 1
-    return rgb, tuple(cnt[k] for k in COUNTERS), dbg, classes
+
+    def texel(code, d):
+        O.lib().cvo_sky_indices(O.CV, C.byref(sky_pos if code == O.POSITIVE else sky_neg), O._dp(d), C.byref(tx), C.byref(ty))
+        return tx.value, ty.value
+    return texel
 
 
-class EscapeAngle:
-    """compute_escape_angle (src/systems.rs:203-261, tail :144-187, :246-252) with scaled steps, from the oracle's primitives"""
-
-    def __init__(self, metric, l, delta, S, max_iter, max_radius):
-        self.w = Walk(metric)
-        self.l, self.delta, self.S, self.max_iter, self.max_radius = l, delta, S, max_iter, max_radius
-        self.inner = strict_radius(metric)
-        self.calls = self.steps = 0
-        self.classes = []       # per call: (code, plain steps, scaled steps, strict-zone steps)
-
-    def __call__(self, alpha):
-        """(code, angle, steps)"""
-        L, w = O.lib(), self.w
-        a1 = np.array([alpha])
-        sa, ca = float(O.math_array(O.CV, 0, a1)[0]), float(O.math_array(O.CV, 1, a1)[0])
-        pos = np.array([0.0, self.l, np.pi / 2.0, 0.0])
-        L.cvo_new_photon(O.CV, w.mp, O._dp(pos), O._dp(np.array([ca, 0.0, sa])), w.xp, w.pp)
-        code, steps, plain, inside = w.run(self.delta, self.S, self.max_iter, self.max_radius, self.inner)
-        self.calls += 1
-        self.steps += steps
-        self.classes.append((code, plain, steps - plain, inside))
-        if code in (O.PANIC, O.NOT_ESCAPED):
-            return code, 0.0, steps
-        tdir, wpos, rot, wd = np.zeros(3), np.zeros(3), np.zeros(9), np.zeros(3)
-        L.cvo_vector_to_direction(O.CV, w.mp, w.pp, w.xp, O._dp(tdir))
-        L.cvo_vector3_from_theta_phi(O.CV, float(w.x[2]), float(w.x[3]), O._dp(wpos))
-        if L.cvo_rotation_from_two_vectors(O.CV, O._dp(np.array([1.0, 0.0, 0.0])), O._dp(wpos), O._dp(rot)) != 0:
-            return O.PANIC, 0.0, steps
-        L.cvo_mat3_vec(O._dp(rot), O._dp(tdir), O._dp(wd))
-        x, y, z = float(wd[0]), float(wd[1]), float(wd[2])
-        n = math.sqrt(x * x + y * y + z * z)
-        x, y, z = x / n, y / n, z / n
-        vx = x * 1.0 + y * 0.0 + z * 0.0
-        vy = x * 0.0 + y * 1.0 + z * 0.0
-        acos = float(O.math_array(O.CV, 3, np.array([vx]))[0])
-        return code, (acos if vy >= 0.0 else 2.0 * np.pi - acos), steps
-
-    def sample(self, alpha):
-        """the closure of src/systems.rs:473-485: (escape angle, escape space), NaN when not escaped"""
-        code, ang, _ = self(alpha)
-        if code == O.POSITIVE:
-            return ang, 1.0
-        if code == O.NEGATIVE:
-            return ang, -1.0
-        assert code != O.PANIC
-        return float("nan"), float("nan")
+def brute(metric, cam, dirs, sky_pos, sky_neg, max_iter, max_radius, delta, S, integrator=0):
+    """the brute renderer's frame with scaled steps: (frame, counters, debug records [H, W] of O.RAY_DEBUG, classes -- per ray (plain
+    steps, scaled steps, strict-zone steps) --, per ray the Heun second stages begun beyond the radius)"""
+    rays = RC.compose_brute(RC.OracleStepper(metric), cam.pos, dirs, max_iter, max_radius, delta, S, integrator, inner=strict_radius(metric))
+    rgb, cnt = RC.frame_nearest(rays, None, (sky_pos, sky_neg))
+    classes = np.stack([rays["plain"], rays["steps"] - rays["plain"], rays["inside"]], axis=-1)
+    return rgb, cnt[:6], RC.debug_records(rays, O.RAY_DEBUG, _texel_of(sky_pos, sky_neg)), classes, rays["beyond"]
 
 
-def sample_table(metric, l, delta, S, max_iter, max_radius, alpha_nums, max_it_sampling, thr1, thr2):
-    """doubly_sample_function over the composed closure: (alpha, escape angle, escape space) arrays, the evaluator (calls, steps, classes)"""
-    f = EscapeAngle(metric, l, delta, S, max_iter, max_radius)
-    a, e, s = ref_python.doubly_sample_function(-0.1 * np.pi, 1.1 * np.pi, alpha_nums, max_it_sampling, thr1, thr2, f.sample)
-    return np.array(a), np.array(e), np.array(s), f
+def direct(metric, cam, dirs, sky_pos, sky_neg, max_iter, max_radius, delta, S, integrator=0):
+    """"direct" mode with scaled steps: (frame, counters, evaluator, per call the Heun second stages begun beyond the radius)"""
+    f = evaluator(metric, cam.pos[1], delta, S, max_iter, max_radius, integrator)
+    rgb, cnt = RC.frame_nearest(RC.compose_direct(f, cam, dirs), None, (sky_pos, sky_neg))
+    return rgb, cnt[:6], f, np.array(f.beyond, np.int64)
 
 
-def compose_efficient(metric, cam, dirs, sky_pos, sky_neg, max_iter, max_radius, delta, S, alpha_nums, max_it_sampling, thr1, thr2):
-    """render_image_efficient over dirs with scaled steps in its sampler: (frame, counters -- steps are the sampler's --, table, evaluator)"""
-    L = O.lib()
-    H, W = dirs.shape[:2]
-    alphas, axes, cam_bg = P.pixel_geometry(cam, dirs)
-    ta, te, ts, f = sample_table(metric, cam.pos[1], delta, S, max_iter, max_radius, alpha_nums, max_it_sampling, thr1, thr2)
-    flat = np.ascontiguousarray(alphas.reshape(-1))
-    esc, spc = np.zeros(flat.size), np.zeros(flat.size)
-    L.cvo_interp_slice(O._dp(ta), O._dp(te), ta.size, O._dp(flat), flat.size, O._dp(esc))
-    L.cvo_interp_slice(O._dp(ta), O._dp(ts), ta.size, O._dp(flat), flat.size, O._dp(spc))
-    esc, spc = esc.reshape(H, W), spc.reshape(H, W)
-    rgb = np.zeros((H, W, 3), np.uint8)
-    cnt = dict.fromkeys(COUNTERS, 0)
-    cnt["steps"] = f.steps
-    for j in range(H):
-        for i in range(W):
-            cnt["rays"] += 1
-            s = spc[j, i]
-            if s == 1.0 or s == -1.0:
-                fin = P._final_direction(axes[j, i], esc[j, i], cam_bg)
-                cnt["n_oob"] += P._shade(sky_pos if s == 1.0 else sky_neg, fin, rgb[j, i])
-                cnt["n_pos" if s == 1.0 else "n_neg"] += 1
-            else:
-                cnt["n_none"] += 1
-    return rgb, tuple(cnt[k] for k in COUNTERS), (ta, te, ts), f
+def efficient(metric, cam, dirs, sky_pos, sky_neg, max_iter, max_radius, delta, S, alpha_nums, max_it_sampling, thr1, thr2, integrator=0):
+    """render_image_efficient with scaled steps in its sampler: (frame, counters -- steps are the sampler's --, table, evaluator, per call
+    the Heun second stages begun beyond the radius)"""
+    f = evaluator(metric, cam.pos[1], delta, S, max_iter, max_radius, integrator)
+    table = RC.sample_table(f, alpha_nums, max_it_sampling, thr1, thr2)
+    rgb, cnt = RC.frame_nearest(RC.compose_efficient(table, cam, dirs), None, (sky_pos, sky_neg), f.steps)
+    return rgb, cnt[:6], table, f, np.array(f.beyond, np.int64)
 
 
-def compose_direct(metric, cam, dirs, sky_pos, sky_neg, max_iter, max_radius, delta, S):
-    """"direct" mode with scaled steps: (frame, counters, evaluator)"""
-    H, W = dirs.shape[:2]
-    alphas, axes, cam_bg = P.pixel_geometry(cam, dirs)
-    f = EscapeAngle(metric, cam.pos[1], delta, S, max_iter, max_radius)
-    rgb = np.zeros((H, W, 3), np.uint8)
-    cnt = dict.fromkeys(COUNTERS, 0)
-    for j in range(H):
-        for i in range(W):
-            code, ang, steps = f(float(alphas[j, i]))
-            cnt["rays"] += 1
-            cnt["steps"] += steps
-            if code in (O.POSITIVE, O.NEGATIVE):
-                fin = P._final_direction(axes[j, i], ang, cam_bg)
-                cnt["n_oob"] += P._shade(sky_pos if code == O.POSITIVE else sky_neg, fin, rgb[j, i])
-                cnt["n_pos" if code == O.POSITIVE else "n_neg"] += 1
-            else:
-                cnt["n_none"] += 1
-    return rgb, tuple(cnt[k] for k in COUNTERS), f
-
-
-def box_average(fine, n):
-    """option "supersample" (include/curvis_hip.h): out = (sum of the n x n block + n^2 / 2) >> (2 log2 n)"""
-    H, W = fine.shape[0] // n, fine.shape[1] // n
-    s = fine.astype(np.uint32).reshape(H, n, W, n, 3).sum(axis=(1, 3))
-    return ((s + n * n // 2) >> (2 * int(math.log2(n)))).astype(np.uint8)
+box_average = RC.box_average
 
 
 # ---- the scenes of the GPU tests ---------------------------------------------------------------------------------------------------
@@ -260,11 +116,7 @@ def cameras(pose, res):
 
 
 def index_skies():
-    if "skies" not in _cache:
-        _cache["skies"] = tuple(common.index_sky(w, h, s) for (w, h), s in zip(SKY_SHAPES, SKY_SALTS))
-        for t in _cache["skies"]:
-            t.setflags(write=False)
-    return _cache["skies"]
+    return RC.index_skies(SKY_SHAPES, SKY_SALTS)
 
 
 def oracle_skies():
@@ -294,11 +146,11 @@ def expected(renderer, kind, pose, S, res=RES, cap=4096, projection=P.PERSPECTIV
         sp, sn = oracle_skies() if skies == "index" else fine_oracle_skies()
         dirs = world_dirs(oc, projection)
         if renderer == "brute":
-            out = compose_brute(om, oc, dirs, sp, sn, cap, max_radius, DELTA, S)
+            out = brute(om, oc, dirs, sp, sn, cap, max_radius, DELTA, S)[:4]
         elif renderer == "direct":
-            out = compose_direct(om, oc, dirs, sp, sn, cap, max_radius, DELTA, S)
+            out = direct(om, oc, dirs, sp, sn, cap, max_radius, DELTA, S)[:3]
         else:
-            out = compose_efficient(om, oc, dirs, sp, sn, cap, max_radius, DELTA, S, EFF["n0"], EFF["maxit"], EFF["t1"], EFF["t2"])
+            out = efficient(om, oc, dirs, sp, sn, cap, max_radius, DELTA, S, EFF["n0"], EFF["maxit"], EFF["t1"], EFF["t2"])[:4]
         out[0].setflags(write=False)
         _cache[key] = out
     return _cache[key]

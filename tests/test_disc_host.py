@@ -131,12 +131,11 @@ def test_disc_crossing_refuses_null_and_empty():
 @pytest.mark.parametrize("name", ("A", "B"))
 def test_without_a_disc_the_composition_is_step_scale_refs(name, S, integrator):
     """pinned first: frame, counters and final states, bit for bit (integrator_ref's composition under Heun)"""
-    import integrator_ref as IR
     _, om, _, oc, _, _ = D.scene(name, res=(13, 9))
     dirs = SR.world_dirs(oc)
     rays = D.walk_rays(D.OracleStepper(om), oc.pos, dirs, None, D.CAP, D.R, D.DELTA, S, integrator)
     rgb, cnt = D.frame_nearest(rays, None, SR.oracle_skies())
-    want = IR.compose_brute(integrator, om, oc, dirs, *SR.oracle_skies(), D.CAP, D.R, D.DELTA, S)
+    want = SR.brute(om, oc, dirs, *SR.oracle_skies(), D.CAP, D.R, D.DELTA, S, integrator)
     assert np.array_equal(rgb, want[0])
     assert cnt[:6] == want[1] and cnt[6] == 0
     assert rays["x"].tobytes() == want[2]["x"].tobytes() and rays["p"].tobytes() == want[2]["p"].tobytes()

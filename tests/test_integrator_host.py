@@ -16,6 +16,7 @@ import common
 import gpu_integrator_cases as CASES
 import integrator_ref as IR
 import oracle_lib as O
+import ref_compose as RC
 import step_scale_ref as SR
 import curvis_amd
 from curvis_amd import _abi, rendering, systems
@@ -40,18 +41,17 @@ def test_euler_compositions_are_step_scale_refs(kind, S):
     sp, sn = SR.oracle_skies()
     dirs = SR.world_dirs(oc)
     brute = (om, oc, dirs, sp, sn, 1500, SR.R, SR.DELTA, S)
-    want, got = SR.compose_brute(*brute), IR.compose_brute(0, *brute)
+    want, got = SR.brute(*brute), SR.brute(*brute, 0)
     assert got[0].tobytes() == want[0].tobytes() and got[1] == want[1] and got[2].tobytes() == want[2].tobytes()
     assert (got[3] == want[3]).all() and (got[4] == 0).all()
-    want, got = SR.compose_direct(*brute), IR.compose_direct(0, *brute)
+    want, got = SR.direct(*brute), SR.direct(*brute, 0)
     assert got[0].tobytes() == want[0].tobytes() and got[1] == want[1]
     eff = brute + (SR.EFF["n0"], SR.EFF["maxit"], SR.EFF["t1"], SR.EFF["t2"])
-    want, got = SR.compose_efficient(*eff), IR.compose_efficient(0, *eff)
+    want, got = SR.efficient(*eff), SR.efficient(*eff, 0)
     assert got[0].tobytes() == want[0].tobytes() and got[1] == want[1]
     assert all(same_bits(g, w) for g, w in zip(got[2], want[2]))
-    assert SR.Walk is not IR.HeunWalk                                    # the name is put back
-    heun = IR.compose_brute(1, *brute)
-    assert heun[1] != want[1] and heun[1][1] != SR.compose_brute(*brute)[1][1]   # and the other walk is another walk
+    heun = SR.brute(*brute, 1)
+    assert heun[1] != want[1] and heun[1][1] != SR.brute(*brute)[1][1]   # and the other walk is another walk
 
 
 # ---- 2. curvis_heun_step is the composition's step --------------------------------------------------------------------------------------
@@ -70,7 +70,7 @@ def assert_state(x, p, w, what):
 def test_heun_step_random_states(kind):
     om, pm = SR.metrics(kind)
     m = pm._c()
-    w = IR.HeunWalk(om)
+    w = RC.Walk(RC.OracleStepper(om))
     rng = np.random.default_rng(21)
     strict, outside, beyond, zero = 0, 0, 0, 0
     inner = SR.strict_radius(om)
@@ -88,7 +88,7 @@ def test_heun_step_random_states(kind):
             l = float(x[1])
         delta = float(np.exp(rng.uniform(np.log(0.01), np.log(2.0))))
         w.x[:], w.p[:] = x, p
-        stage_l = w.step(delta)
+        stage_l = w.heun(delta)
         heun(m, x, p, delta)
         assert_state(x, p, w, (kind, trial))
         strict += inner is not None and abs(l) < inner
@@ -125,7 +125,7 @@ def test_host_walk_reaches_the_composed_state(kind, S):
     om, pm = SR.metrics(kind)
     m = pm._c()
     rng = np.random.default_rng(100 + S)
-    w = IR.HeunWalk(om)
+    w = RC.Walk(RC.OracleStepper(om))
     step = _abi.lib().curvis_step_delta
     dk = C.c_double()
     both, escaped = 0, 0
@@ -135,7 +135,7 @@ def test_host_walk_reaches_the_composed_state(kind, S):
         d = rng.normal(size=3)
         O.lib().cvo_new_photon(O.CV, w.mp, O._dp(pos), O._dp(d), w.xp, w.pp)
         x, p = w.x.copy(), w.p.copy()
-        code, steps, plain, _ = w.run(IR.DELTA, S, 1000, SR.R)
+        code, steps, plain = w.run(IR.DELTA, S, 1, 1000, SR.R)[:3]
         k = 0
         while k < 1000:
             assert step(IR.DELTA, S, float(x[1]), C.byref(dk)) == 0

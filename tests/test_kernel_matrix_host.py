@@ -1,7 +1,7 @@
 """The kernel lattice of the brute renderer (tests/kernel_matrix_ref.py), the parts that need no GPU: the enumeration; the ray classes
 of every walk that tests/test_gpu_kernel_matrix.py compares against, asserted from the reference alone; that every axis of the lattice
 engages in the reference (another lookup, a disc, another step form give another frame or other counters); the reference without a
-disc pinned to step_scale_ref.compose_brute -- schwarzschild_ref.compose_brute for the Schwarzschild kind --, every pixel and every
+disc pinned to step_scale_ref.brute -- schwarzschild_ref.compose_brute, over curvis_walk_ray, for the Schwarzschild kind --, every pixel and every
 counter; and the conditions of the two edge scenes of the disc loop."""
 import numpy as np
 import pytest
@@ -92,7 +92,7 @@ def test_without_a_disc_a_cell_is_step_scale_refs_composition(kind):
     _, om, _, oc, _, _ = K.cell_scene(kind, n)
     S, integrator = K.STEP_WALKS[step]
     assert integrator == 0
-    want = SR.compose_brute(om, oc, SR.world_dirs(oc, K.PROJECTION_OPTION[projection]), *SR.oracle_skies(), K.CAP, K.R, K.DELTA, S)
+    want = SR.brute(om, oc, SR.world_dirs(oc, K.PROJECTION_OPTION[projection]), *SR.oracle_skies(), K.CAP, K.R, K.DELTA, S)
     got = K.cell_frame(kind, step, n, "nearest", projection, False)
     assert np.array_equal(got[0], want[0] if n == 1 else SR.box_average(want[0], n))
     assert got[1][:6] == want[1] and got[1][6] == 0

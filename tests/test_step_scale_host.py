@@ -15,6 +15,7 @@ import pytest
 import common
 import oracle_lib as O
 import projection_ref as P
+import ref_compose as RC
 import step_scale_ref as SR
 import curvis_amd
 from curvis_amd import _abi, rendering, systems
@@ -31,7 +32,7 @@ KINDS = ("ellis", "interstellar", "flat")
 def test_walk_reproduces_escape_photon(kind):
     om = SR.metrics(kind)[0]
     rng = np.random.default_rng(11)
-    w = SR.Walk(om)
+    w = RC.Walk(RC.OracleStepper(om))
     seen = set()
     for trial in range(60):
         l = float(rng.uniform(-6.0, 6.0)) if kind != "flat" else float(rng.uniform(0.5, 6.0))
@@ -40,8 +41,8 @@ def test_walk_reproduces_escape_photon(kind):
         cap = 300 if trial % 5 == 0 else 4096
         code, steps, x, p = O.escape_photon(O.CV, om, pos, d, SR.DELTA, cap, SR.R)
         O.lib().cvo_new_photon(O.CV, w.mp, O._dp(pos), O._dp(d), w.xp, w.pp)
-        got = w.run(SR.DELTA, 0, cap, SR.R)
-        assert got[:2] == (code, steps) and got[2] == steps
+        got = w.run(SR.DELTA, 0, 0, cap, SR.R)
+        assert got[:2] == (code, steps) and got.plain == steps
         assert common.bits(w.x).tobytes() == common.bits(x).tobytes() and common.bits(w.p).tobytes() == common.bits(p).tobytes()
         seen.add(code)
     assert O.NOT_ESCAPED in seen and O.POSITIVE in seen and (kind == "flat" or O.NEGATIVE in seen)
@@ -51,7 +52,7 @@ def test_walk_reproduces_escape_photon(kind):
 def test_escape_angle_reproduces_the_oracle(kind):
     om = SR.metrics(kind)[0]
     l = 3.0
-    f = SR.EscapeAngle(om, l, SR.DELTA, 0, 1500, SR.R)
+    f = SR.evaluator(om, l, SR.DELTA, 0, 1500, SR.R)
     alphas = np.linspace(-0.1 * np.pi, 1.1 * np.pi, 2001)
     sides = {O.POSITIVE: 0, O.NEGATIVE: 0, O.NOT_ESCAPED: 0, O.PANIC: 0}
     for a in alphas:
@@ -73,7 +74,8 @@ def test_sample_table_reproduces_the_oracle(kind):
     want = [np.ctypeslib.as_array(getattr(smp, k), (smp.n,)).copy() for k in "aes"]
     calls, steps = int(smp.calls), int(smp.steps)
     O.lib().cvo_samples_free(C.byref(smp))
-    a, e, s, f = SR.sample_table(om, 3.0, SR.DELTA, 0, *args)
+    f = SR.evaluator(om, 3.0, SR.DELTA, 0, *args[:2])
+    a, e, s = RC.sample_table(f, *args[2:])
     for got, w in zip((a, e, s), want):
         assert common.bits(got).tobytes() == common.bits(w).tobytes()
     assert (f.calls, f.steps) == (calls, steps)
@@ -87,16 +89,16 @@ def test_frames_reproduce_the_oracle(kind):
     dirs = SR.world_dirs(oc)
     cap = 1500
     want, wdbg, st = O.render_image(O.CV, om, oc, sp, sn, cap, SR.R, SR.DELTA, debug=True)
-    got, cnt, dbg, _ = SR.compose_brute(om, oc, dirs, sp, sn, cap, SR.R, SR.DELTA, 0)
+    got, cnt, dbg, _, _ = SR.brute(om, oc, dirs, sp, sn, cap, SR.R, SR.DELTA, 0)
     assert got.tobytes() == want.tobytes() and cnt == tuple(int(getattr(st, k)) for k in SR.COUNTERS)
     common.assert_debug_equal(dbg, wdbg)
     eff = (cap, SR.R, SR.DELTA, SR.EFF["n0"], SR.EFF["maxit"], SR.EFF["t1"], SR.EFF["t2"])
     want, smp, st = O.render_image_efficient(O.CV, om, oc, sp, sn, *eff)
-    got, cnt, tab, _ = SR.compose_efficient(om, oc, dirs, sp, sn, cap, SR.R, SR.DELTA, 0, *eff[3:])
+    got, cnt, tab, _, _ = SR.efficient(om, oc, dirs, sp, sn, cap, SR.R, SR.DELTA, 0, *eff[3:])
     assert got.tobytes() == want.tobytes() and cnt == tuple(int(getattr(st, k)) for k in SR.COUNTERS)
     assert common.bits(tab[0]).tobytes() == common.bits(smp["a"]).tobytes()
     want, st = O.render_image_direct(O.CV, om, oc, sp, sn, cap, SR.R, SR.DELTA)
-    got, cnt, _ = SR.compose_direct(om, oc, dirs, sp, sn, cap, SR.R, SR.DELTA, 0)
+    got, cnt, _, _ = SR.direct(om, oc, dirs, sp, sn, cap, SR.R, SR.DELTA, 0)
     assert got.tobytes() == want.tobytes() and cnt == tuple(int(getattr(st, k)) for k in SR.COUNTERS)
 
 
@@ -172,7 +174,7 @@ def test_host_walk_reaches_the_composed_state(kind, S):
     om, pm = SR.metrics(kind)
     m = pm._c()
     rng = np.random.default_rng(S)
-    w = SR.Walk(om)
+    w = RC.Walk(RC.OracleStepper(om))
     step, upd = _abi.lib().curvis_step_delta, _abi.lib().curvis_update_relativistic_object
     dk = C.c_double()
     both = 0
@@ -182,7 +184,7 @@ def test_host_walk_reaches_the_composed_state(kind, S):
         d = rng.normal(size=3)
         O.lib().cvo_new_photon(O.CV, w.mp, O._dp(pos), O._dp(d), w.xp, w.pp)
         x, p = w.x.copy(), w.p.copy()
-        code, steps, plain, _ = w.run(SR.DELTA, S, 2000, SR.R)
+        code, steps, plain = w.run(SR.DELTA, S, 0, 2000, SR.R)[:3]
         k = 0
         while k < 2000:
             assert step(SR.DELTA, S, float(x[1]), C.byref(dk)) == 0

@@ -25,6 +25,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import oracle_lib as O  # noqa: E402
+import ref_compose as RC  # noqa: E402
 import step_scale_ref as SR  # noqa: E402
 from curvis_amd import rendering  # noqa: E402
 
@@ -40,7 +41,7 @@ def final_directions(metric, cam, dirs, delta, S, cap):
     flat = dirs.reshape(-1, 3)
     codes, out, steps = np.zeros(len(flat), np.int64), np.zeros((len(flat), 3)), np.zeros(len(flat), np.int64)
     pos = np.array(cam.pos[:])
-    w = SR.Walk(metric)
+    w = RC.Walk(RC.OracleStepper(metric))
     d = np.zeros(3)
     n = C.c_uint32(0)
     for i, v in enumerate(flat):
@@ -49,7 +50,7 @@ def final_directions(metric, cam, dirs, delta, S, cap):
             codes[i] = L.cvo_escape_photon(O.CV, w.mp, w.xp, w.pp, delta, cap, R, C.byref(n))
             steps[i] = n.value
         else:
-            codes[i], steps[i] = w.run(delta, S, cap, R)[:2]
+            codes[i], steps[i] = w.run(delta, S, 0, cap, R)[:2]
         if codes[i] in (O.POSITIVE, O.NEGATIVE):
             L.cvo_vector_to_direction(O.CV, w.mp, w.pp, w.xp, O._dp(d))
             out[i] = d / np.sqrt(d @ d)
