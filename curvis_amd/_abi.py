@@ -83,6 +83,10 @@ SYMBOLS = {
     "curvis_metric_tensor": (C.c_int, [C.POINTER(Metric), _dp, _dp, _dp]),
     "curvis_camera_outward_vector": (C.c_int, [C.POINTER(CameraC), C.c_uint32, C.c_uint32, _dp, _dp]),
     "curvis_camera_outward_vector_projected": (C.c_int, [C.POINTER(CameraC), C.c_int32, C.c_uint32, C.c_uint32, _dp, _dp]),
+    "curvis_ctx_set_camera_velocities": (C.c_int, [_vp, _dp, C.c_uint32]),
+    "curvis_camera_boost_prepare": (C.c_int, [C.POINTER(CameraC), _dp, _dp]),
+    "curvis_camera_outward_vector_boosted": (C.c_int, [C.POINTER(CameraC), C.c_int32, _dp, C.c_uint32, C.c_uint32, _dp, _dp]),
+    "curvis_camera_path_velocity": (C.c_int, [C.POINTER(Metric), _dp, _dp, _dp, C.c_double, _dp]),
     "curvis_vector_to_direction": (C.c_int, [C.POINTER(Metric), _dp, _dp, _dp]),
     "curvis_update_relativistic_object": (C.c_int, [C.POINTER(Metric), _dp, _dp, C.c_double]),
     "curvis_step_delta": (C.c_int, [C.c_double, C.c_int64, C.c_double, _dp]),

@@ -610,6 +610,69 @@ int curvis_camera_outward_vector_projected(const curvis_camera *camera, int32_t 
   return CURVIS_OK;
 }
 
+int curvis_ctx_set_camera_velocities(curvis_ctx *ctx, const double *beta, uint32_t n) {
+  if (!ctx) return CURVIS_E_INVALID;
+  if (!beta || n == 0) {
+    ctx->cam_beta.clear();
+    return CURVIS_OK;
+  }
+  for (uint32_t k = 0; k < n; ++k) {
+    const double *b = beta + 3 * (size_t)k;
+    if (!((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2] < 1.0))
+      return fail(ctx, CURVIS_E_INVALID, "camera velocity: the speed of triple " + std::to_string(k) + " is not below 1 (the speed of light)");
+  }
+  ctx->cam_beta.assign(beta, beta + 3 * (size_t)n);
+  return CURVIS_OK;
+}
+
+int curvis_camera_boost_prepare(const curvis_camera *camera, const double beta[3], double out[5]) {
+  if (!camera || !beta || !out) return CURVIS_E_INVALID;
+  cvk::CameraBoost K;
+  if (cvk::camera_boost_prepare(camera->rot, beta, K) < 0) return CURVIS_E_INVALID;
+  out[0] = K.u[0], out[1] = K.u[1], out[2] = K.u[2], out[3] = K.A, out[4] = K.B;
+  return CURVIS_OK;
+}
+
+int curvis_camera_outward_vector_boosted(const curvis_camera *camera, int32_t projection, const double beta[3], uint32_t px, uint32_t py,
+                                         double camera_space[3], double world_space[3]) {
+  if (!camera || !beta || camera->res_x == 0 || camera->res_y == 0 || projection < 0 || projection > 2) return CURVIS_E_INVALID;
+  /* the first half of cvk::ray_init, by the functions it calls */
+  const cvk::CameraParams C = make_camera(*camera);
+  cvk::CameraBoost K;
+  if (cvk::camera_boost_prepare(C.rot, beta, K) < 0) return CURVIS_E_INVALID;
+  double vx, vy, vz;
+  cvk::camera_pixel_vector(C, (int)projection, px, py, vx, vy, vz);
+  cvk::camera_boost(K, vx, vy, vz);
+  const double n = std::sqrt(vx * vx + vy * vy + vz * vz);
+  vx = vx / n;
+  vy = vy / n;
+  vz = vz / n;
+  if (camera_space) {
+    camera_space[0] = vx;
+    camera_space[1] = vy;
+    camera_space[2] = vz;
+  }
+  if (world_space) cvk::mat3_vec(C.rot, vx, vy, vz, world_space[0], world_space[1], world_space[2]);
+  return CURVIS_OK;
+}
+
+int curvis_camera_path_velocity(const curvis_metric *metric, const double pos_prev[4], const double pos[4], const double pos_next[4],
+                                double light_speed, double beta_out[3]) {
+  if (!metric || !pos_prev || !pos || !pos_next || !beta_out) return CURVIS_E_INVALID;
+  double r;
+  if (const int rc = curvis_metric_functions(metric, pos[1], &r, nullptr, nullptr)) return rc;
+  const double dt = pos_next[0] - pos_prev[0];
+  if (dt == 0.0) {
+    beta_out[0] = beta_out[1] = beta_out[2] = 0.0;
+    return CURVIS_OK;
+  }
+  const double inv = 1.0 / (dt * light_speed);
+  beta_out[0] = (pos_next[1] - pos_prev[1]) * inv;
+  beta_out[1] = r * (pos_next[2] - pos_prev[2]) * inv;
+  beta_out[2] = (r * cv_sin(pos[2])) * (pos_next[3] - pos_prev[3]) * inv;
+  return CURVIS_OK;
+}
+
 int curvis_vector_to_direction(const curvis_metric *metric, const double position[4], const double p_cov[4],
                                double direction[3]) {
   if (!metric || !position || !p_cov || !direction) return CURVIS_E_INVALID;

@@ -703,11 +703,55 @@ __attribute__((always_inline)) CV_HD void camera_pixel_vector(const CameraParams
   vz = sb * (zs / rho);
 }
 
-/* pixel -> photon: src/cameras.rs:150-172 then src/metrics.rs:301-334; projection: camera_pixel_vector above */
-template <int KIND>
-CV_HD void ray_init(const MetricParams &M, const CameraParams &C, unsigned px, unsigned py, Ray &q, int projection = PROJ_PERSPECTIVE) {
+/* ---- the moving camera (curvis_ctx_set_camera_velocities; include/curvis_hip.h has the definition, the lines below are its steps in
+ * its order, every operation one rounded FP64 operation).  A frame's velocity becomes five doubles once per frame on the host
+ * (camera_boost_prepare); camera_boost then turns the un-normalised camera-space vector of a pixel of the MOVING camera into that of
+ * the static observer at the same place, between camera_pixel_vector and the normalisation that follows it.  Nothing else of a
+ * renderer knows about the motion.  The kernels that hold it are the PROJ = 1 ones: their `projection` argument carries PROJ_BOOSTED
+ * on top of the projection's number, a launch-uniform bit, so the boost sits behind a scalar branch and a call without a velocity
+ * runs the instructions it ran before. */
+enum { PROJ_BOOSTED = 0x100, PROJ_KIND_MASK = 0xFF };
+struct CameraBoost {
+  double u[3]; /* the camera-space direction of travel */
+  double A, B; /* gamma - 1 and gamma beta; B == 0 says "not boosted" (a boosted frame has B > 0) */
+};
+/* rot: the camera's 3 x 3, row-major; beta: (b_l, b_theta, b_phi).  Returns 1 boosted, 0 not boosted (K all zeros), -1 for a speed that
+ * is not below 1 (a NaN included) */
+CV_HD int camera_boost_prepare(const double *rot, const double *beta, CameraBoost &K) {
+  double c[3];
+  for (int i = 0; i < 3; ++i) c[i] = ((rot[i] * beta[0]) + rot[3 + i] * beta[1]) + rot[6 + i] * beta[2];
+  const double b2 = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2];
+  K.u[0] = K.u[1] = K.u[2] = K.A = K.B = 0.0;
+  if (b2 == 0.0) return 0;
+  if (!(b2 < 1.0)) return -1;
+  const double b = CV_SQRT(b2), g = 1.0 / CV_SQRT(1.0 - b2);
+  for (int i = 0; i < 3; ++i) K.u[i] = c[i] / b;
+  K.A = g - 1.0;
+  K.B = g * b;
+  return 1;
+}
+/* SHARED (the efficient pixel kernel): the square root is sqrt_plain's, which returns the correctly rounded root like the operator;
+ * the rest is products and sums */
+template <bool SHARED = false>
+__attribute__((always_inline)) CV_HD void camera_boost(const CameraBoost &K, double &vx, double &vy, double &vz) {
+  if (K.B == 0.0) return; /* a frame at rest in a call whose other frames move: its vector keeps its bits, the sign of a zero included */
+  const double n = sqrt_plain<SHARED>((vx * vx + vy * vy) + vz * vz);
+  const double p = (vx * K.u[0] + vy * K.u[1]) + vz * K.u[2];
+  const double s = K.A * p - K.B * n;
+  vx = vx + K.u[0] * s;
+  vy = vy + K.u[1] * s;
+  vz = vz + K.u[2] * s;
+}
+
+/* pixel -> photon: src/cameras.rs:150-172 then src/metrics.rs:301-334; projection: camera_pixel_vector above, with PROJ_BOOSTED on top
+ * while the frame has a velocity (B: its CameraBoost, read only then) */
+template <int KIND, bool BOOST = false> /* BOOST: the instantiation the PROJ = 1 kernels call; the other is the function it was, text for text */
+CV_HD void ray_init(const MetricParams &M, const CameraParams &C, unsigned px, unsigned py, Ray &q, int projection = PROJ_PERSPECTIVE,
+                    const CameraBoost *B = nullptr) {
   double vx, vy, vz;
-  camera_pixel_vector(C, projection, px, py, vx, vy, vz);
+  camera_pixel_vector(C, BOOST ? projection & PROJ_KIND_MASK : projection, px, py, vx, vy, vz);
+  if constexpr (BOOST)
+    if (projection & PROJ_BOOSTED) camera_boost(*B, vx, vy, vz);
   double n = CV_SQRT(vx * vx + vy * vy + vz * vz); /* Vector3::normalize */
   vx = vx / n;
   vy = vy / n;

@@ -212,10 +212,12 @@ CV_HD unsigned interp_index_grid(const double *x, unsigned n, double xp, const u
  * outward direction and the radial direction, and the rotation axis cam_bg x out_bg */
 template <bool SHARED = false>
 CV_HD void efficient_pixel_geometry(const CameraParams &C, const EfficientFrame &F, unsigned px, unsigned py, double &alpha,
-                                    double *axis, const PixelRecips *R = nullptr, int projection = PROJ_PERSPECTIVE) {
-  /* outward_vector_on_world_space_from_x_y (src/cameras.rs:150-172), or option "projection" */
+                                    double *axis, const PixelRecips *R = nullptr, int projection = PROJ_PERSPECTIVE,
+                                    const CameraBoost *B = nullptr) {
+  /* outward_vector_on_world_space_from_x_y (src/cameras.rs:150-172), or option "projection"; PROJ_BOOSTED: the frame's camera moves */
   double v0[3];
-  camera_pixel_vector<SHARED>(C, projection, px, py, v0[0], v0[1], v0[2], R);
+  camera_pixel_vector<SHARED>(C, projection & PROJ_KIND_MASK, px, py, v0[0], v0[1], v0[2], R);
+  if (projection & PROJ_BOOSTED) camera_boost<SHARED>(*B, v0[0], v0[1], v0[2]);
   const double n = sqrt_plain<SHARED>(dot3(v0, v0)); /* norm3 */
   double v[3];
   unit3<SHARED>(v0, n, v);
@@ -243,9 +245,9 @@ template <bool SHARED = false>
 CV_HD void efficient_pixel(const CameraParams &C, const EfficientFrame &F, unsigned px, unsigned py,
                            const double *sx, const double *m_e, const double *c_e, const double *m_s,
                            const double *c_s, unsigned n_samples, double *fin, double &space, const PixelRecips *R = nullptr,
-                           const unsigned *grid = nullptr, int projection = PROJ_PERSPECTIVE) {
+                           const unsigned *grid = nullptr, int projection = PROJ_PERSPECTIVE, const CameraBoost *B = nullptr) {
   double alpha, axis[3];
-  efficient_pixel_geometry<SHARED>(C, F, px, py, alpha, axis, R, projection);
+  efficient_pixel_geometry<SHARED>(C, F, px, py, alpha, axis, R, projection, B);
   double esc;
   if (n_samples == 0) { /* interp_slice on empty tables returns zeros */
     esc = 0.0;

@@ -16,7 +16,8 @@ struct EfficientCall {
   uint32_t alpha_nums, max_iterations_sampling;
   double thr1, thr2;
   uint32_t filter = 0; /* option "sky_filter" for this call */
-  uint32_t projection = 0; /* option "projection" for this call */
+  uint32_t projection = 0; /* option "projection" for this call (CallShape: with PROJ_BOOSTED while a frame moves) */
+  const cvk::CameraBoost *boost = nullptr; /* ... and then the frames' boosts, n_frames of them */
   uint32_t ss = 1; /* supersampling factor: with ss > 1 `cams` are those of the ss times finer pixel grid (render_efficient_impl) */
   double kappa = 0.0; /* option "step_scale" for this call: RN(delta / L0) ... */
   int adapt = 0; /* ... and the kernels' ADAPT (CallShape): 1 the samplers integrate with step_delta, 2 option "integrator" = 1, with Heun steps */
@@ -480,13 +481,12 @@ int render_efficient_device(curvis_ctx *ctx, const EfficientCall &c, const cvk::
     off += (bytes + 255) & ~(size_t)255;
     return o;
   };
-  const size_t o_cams = carve(sizeof(cvk::CameraParams) * n_frames), o_fr = carve(sizeof(cvk::EfficientFrame) * n_frames);
+  const size_t o_cams = carve(staged_cameras_bytes(n_frames, c.boost)), o_fr = carve(sizeof(cvk::EfficientFrame) * n_frames);
   if ((rc = ctx->d_eff.reserve(ctx, off))) return rc;
   if ((rc = ctx->h_eff.reserve(ctx, off, off / 2))) return rc;
   unsigned char *stage = ctx->h_eff;
   {
-    auto *cp = reinterpret_cast<cvk::CameraParams *>(stage + o_cams);
-    for (uint32_t f = 0; f < n_frames; ++f) cp[f] = make_camera(c.cams[f]);
+    stage_cameras(stage + o_cams, c.cams, n_frames, c.boost);
     std::memcpy(stage + o_fr, eframes.data(), sizeof(cvk::EfficientFrame) * n_frames);
   }
   const size_t fb_bytes = (size_t)(W / c.ss) * (H / c.ss) * 3 * n_frames; /* W x H: the (fine) pixel grid; frames are W/ss x H/ss */
@@ -839,16 +839,14 @@ int render_pixels_staged(curvis_ctx *ctx, const EfficientCall &c, const std::vec
     off += (bytes + 15) & ~(size_t)15;
     return o;
   };
-  const size_t o_cams = carve(sizeof(cvk::CameraParams) * n_frames), o_fr = carve(sizeof(cvk::EfficientFrame) * n_frames),
+  const size_t o_cams = carve(staged_cameras_bytes(n_frames, c.boost)), o_fr = carve(sizeof(cvk::EfficientFrame) * n_frames),
                o_to = carve(sizeof(unsigned) * n_frames), o_tn = carve(sizeof(unsigned) * n_frames),
                o_go = carve(sizeof(unsigned) * n_frames), o_gr = carve(sizeof(unsigned) * t.grid.size()),
                o_sx = carve(sizeof(double) * T), o_me = carve(sizeof(double) * T), o_ce = carve(sizeof(double) * T),
                o_ms = carve(sizeof(double) * T), o_cs = carve(sizeof(double) * T);
   if ((rc = ctx->d_eff.reserve(ctx, off))) return rc;
   std::vector<unsigned char> stage(off);
-  std::vector<cvk::CameraParams> cp(n_frames);
-  for (uint32_t f = 0; f < n_frames; ++f) cp[f] = make_camera(c.cams[f]);
-  std::memcpy(stage.data() + o_cams, cp.data(), sizeof(cvk::CameraParams) * n_frames);
+  stage_cameras(stage.data() + o_cams, c.cams, n_frames, c.boost);
   std::memcpy(stage.data() + o_fr, eframes.data(), sizeof(cvk::EfficientFrame) * n_frames);
   std::memcpy(stage.data() + o_to, t.tab_off.data(), sizeof(unsigned) * n_frames);
   std::memcpy(stage.data() + o_tn, t.tab_n.data(), sizeof(unsigned) * n_frames);
@@ -899,6 +897,7 @@ int render_efficient_impl(curvis_ctx *ctx, const EfficientCall &call, uint8_t *r
   c.ss = shape.ss;
   c.filter = shape.filter;
   c.projection = shape.projection;
+  c.boost = shape.boost.empty() ? nullptr : shape.boost.data();
   const curvis_metric *metric = c.metric;
   const curvis_camera *cams = c.cams;
   const uint32_t n_frames = c.n_frames, alpha_nums = c.alpha_nums;
@@ -979,13 +978,14 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   int rc = curvis_metric_validate(metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   /* option "supersample" = N > 1: the camera of the N times finer grid, averaged into res_x x res_y by the kernel's epilogue */
-  DirectParamsAdapt P;
+  WithCameraBoost<DirectParamsAdapt> P; /* the widest argument: every form's is a base of it, or (FILTER = 2) built from one */
   CallShape shape;
   if ((rc = schwarzschild_camera_check(ctx, metric, cam, 1))) return rc;
   if ((rc = prepare_call_shape(ctx, cam, 1, delta, "frame too large", shape))) return rc;
   P.kappa = shape.kappa;
   const uint32_t ss = shape.ss, filter = shape.filter;
   P.projection = (int)shape.projection;
+  P.boost = shape.boost.empty() ? cvk::CameraBoost{} : shape.boost[0];
   const uint32_t W = cam->res_x, H = cam->res_y;
   if (W == 0 || H == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
   if (std::fabs(cam->pos[1]) > max_radius)
@@ -1024,14 +1024,14 @@ int render_direct_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvi
   with_launch_shape(metric->kind, ctx->fast_math != 0, ss, filter, shape.projection, shape.adapt, [&](auto S) {
     using T = decltype(S);
     const dim3 grid((unsigned)((P.total_rays + 255ull) / 256ull));
+    DirectArgs<T::ADAPT, T::FILTER, T::PROJ> A; /* the form's own argument: the boost behind PROJ = 1, the level tables behind FILTER = 2 */
+    static_cast<std::conditional_t<T::ADAPT != 0, DirectParamsAdapt, DirectParams> &>(A) = P;
+    if constexpr (T::PROJ != 0) A.boost = P.boost;
     if constexpr (T::FILTER == 2) {
-      using Base = std::conditional_t<T::ADAPT != 0, DirectParamsAdapt, DirectParams>;
-      WithSkyMip<Base> PM;
-      static_cast<Base &>(PM) = P;
-      PM.mip = sky_mip_args(ctx);
-      hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, 2, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, PM);
-    } else if constexpr (T::ADAPT != 0) hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, P);
-    else hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, static_cast<const DirectParams &>(P));
+      A.mip = sky_mip_args(ctx);
+      hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, 2, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, A);
+    } else if constexpr (T::ADAPT != 0) hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>), grid, dim3(256), 0, ctx->stream, A);
+    else hipLaunchKernelGGL((direct_kernel<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ>), grid, dim3(256), 0, ctx->stream, A);
   });
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));

@@ -30,6 +30,11 @@ struct Args {
                                              (curvis_ctx_set_disc_motion); with --disc only, a motion only under a metric file with `mass` */
   int disc_motion = 0;
   double disc_gain = 1.0;
+  std::string camera_velocity_s; /* image: --camera-velocity BL,BTH,BPH, the camera's velocity in units of c (curvis_ctx_set_camera_velocities) */
+  double camera_velocity[3] = {0.0, 0.0, 0.0};
+  std::string camera_motion = "static", light_speed_s; /* video: --camera-motion static|path --light-speed C: every frame's velocity from the
+                                                          path (curvis_camera_path_velocity), C path units per unit of path time */
+  double light_speed = 1.0;
 };
 /* the disc of the run (Args::disc, decoded by load_common) for make_ctx_bare: every context gets it */
 struct DiscOfRun {
@@ -45,6 +50,8 @@ int g_sky_mipmap = 0;  /* Args::sky_mipmap, likewise */
 int g_projection = 0;  /* Args::projection, likewise */
 long long g_step_scale = 0; /* Args::step_scale, likewise */
 int g_integrator = 0;  /* Args::integrator, likewise */
+bool g_camera_velocity_set = false; /* Args::camera_velocity (`curvis image`), likewise */
+double g_camera_velocity[3] = {0.0, 0.0, 0.0};
 [[noreturn]] void die(const std::string &msg, int code = 1) {
   std::fprintf(stderr, "%s\n", msg.c_str());
   std::exit(code);
@@ -62,7 +69,9 @@ void usage() {
       "              [--projection perspective|equirectangular|fisheye] [--step-scale L0]\n"
       "              [--integrator euler|heun] [--sky-mipmap on|off]\n"
       "              [--disc <IMAGE FILE> --disc-inner L --disc-outer L]  (an accretion disc; needs --mode brute)\n"
-      "              [--disc-motion static|prograde|retrograde] [--disc-gain G]  (with --disc; a motion needs a metric file with `mass`)\n");
+      "              [--disc-motion static|prograde|retrograde] [--disc-gain G]  (with --disc; a motion needs a metric file with `mass`)\n"
+      "              image: [--camera-velocity BL,BTH,BPH]  (the camera moves: aberration; units of c)\n"
+      "              video: [--camera-motion static|path] [--light-speed C]  (every frame's velocity from the camera path)\n");
 }
 Args parse_args(int argc, char **argv) {
   Args a;
@@ -144,6 +153,9 @@ Args parse_args(int argc, char **argv) {
       if (val != "euler" && val != "heun") die("error: --integrator must be euler or heun", 2);
       a.integrator = g_integrator = val == "heun" ? 1 : 0;
     }
+    else if (key == "--camera-velocity") take(a.camera_velocity_s);
+    else if (key == "--camera-motion") take(a.camera_motion);
+    else if (key == "--light-speed") take(a.light_speed_s);
     else if (key == "--disc") take(a.disc);
     else if (key == "--disc-inner") take(a.disc_inner_s);
     else if (key == "--disc-outer") take(a.disc_outer_s);
@@ -189,6 +201,30 @@ Args parse_args(int argc, char **argv) {
       a.disc_gain = std::strtod(a.disc_gain_s.c_str(), &end);
       if (*end != '\0' || !std::isfinite(a.disc_gain) || a.disc_gain < 0.0) die("error: --disc-gain must be a finite number, not negative", 2);
     }
+  }
+  if (!a.camera_velocity_s.empty()) {
+    if (a.sub != "image") die("error: --camera-velocity belongs to `curvis image` (a video takes --camera-motion path)", 2);
+    char *end = nullptr;
+    const char *p = a.camera_velocity_s.c_str();
+    bool ok = true;
+    for (int i = 0; i < 3 && ok; ++i) {
+      a.camera_velocity[i] = std::strtod(p, &end);
+      ok = end != p && *end == (i < 2 ? ',' : '\0');
+      p = end + 1;
+    }
+    const double *b = a.camera_velocity;
+    if (!ok || !((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2] < 1.0))
+      die("error: --camera-velocity must be BL,BTH,BPH, three numbers with a speed below 1 (the speed of light)", 2);
+    g_camera_velocity_set = true;
+    for (int i = 0; i < 3; ++i) g_camera_velocity[i] = b[i];
+  }
+  if (a.camera_motion != "static" && a.camera_motion != "path") die("error: --camera-motion must be static or path", 2);
+  if (a.camera_motion != "static" && a.sub != "video") die("error: --camera-motion belongs to `curvis video` (an image takes --camera-velocity)", 2);
+  if (!a.light_speed_s.empty()) {
+    char *end = nullptr;
+    a.light_speed = std::strtod(a.light_speed_s.c_str(), &end);
+    if (*end != '\0' || !std::isfinite(a.light_speed) || !(a.light_speed > 0.0)) die("error: --light-speed must be a positive number", 2);
+    if (a.camera_motion != "path") die("error: --light-speed needs --camera-motion path", 2);
   }
   if (a.sky_broadcast != "rccl" && a.sky_broadcast != "upload") die("error: --sky-broadcast must be rccl or upload", 2);
   if (a.gpu_png != "auto" && a.gpu_png != "on" && a.gpu_png != "off") die("error: --gpu-png must be auto, on or off", 2);
@@ -361,6 +397,7 @@ curvis_ctx *make_ctx_bare(int device, const char *what) {
   if (g_integrator != 0) check(curvis_ctx_set_option(ctx, "integrator", g_integrator), ctx, what);
   if (g_disc.set) check(curvis_ctx_set_disc(ctx, g_disc.img.rgba.data(), g_disc.img.w, g_disc.img.h, g_disc.l_inner, g_disc.l_outer), ctx, what);
   if (g_disc.set && (g_disc.motion != 0 || g_disc.gain != 1.0)) check(curvis_ctx_set_disc_motion(ctx, g_disc.motion, g_disc.gain), ctx, what);
+  if (g_camera_velocity_set) check(curvis_ctx_set_camera_velocities(ctx, g_camera_velocity, 1), ctx, what);
   return ctx;
 }
 void upload_skies(curvis_ctx *ctx, const Common &c, const char *what) {
@@ -386,8 +423,11 @@ void prefetch_frames(curvis_ctx *ctx, const Args &a, const Common &c, const curv
  * the batch calls of the other modes keep theirs inside the context: curvis_ctx_frame_stats) */
 thread_local std::vector<curvis_stats> g_direct_frame_stats;
 
+/* beta (video, --camera-motion path): the n frames' velocities, set on the context before the call that renders them */
 int render_frames(curvis_ctx *ctx, const Args &a, const Common &c, const curvis_camera *cams, uint32_t n, double thr2,
-                  uint8_t *rgb, curvis_stats *st) {
+                  uint8_t *rgb, curvis_stats *st, const double *beta = nullptr) {
+  if (beta && a.mode != "direct")
+    if (const int rc = curvis_ctx_set_camera_velocities(ctx, beta, n)) return rc;
   if (a.mode == "brute")
     return curvis_render_brute_batch(ctx, &c.metric, cams, n, c.sim.ray_integration_max_itarations, c.sim.escape_radius,
                                      c.sim.ray_integration_step, rgb, st);
@@ -398,6 +438,8 @@ int render_frames(curvis_ctx *ctx, const Args &a, const Common &c, const curvis_
     g_direct_frame_stats.clear();
     for (uint32_t f = 0; f < n; ++f) {
       curvis_stats one;
+      if (beta)
+        if (const int brc = curvis_ctx_set_camera_velocities(ctx, beta + 3 * (size_t)f, 1)) return brc;
       const int rc = curvis_render_direct(ctx, &c.metric, cams + f, c.sim.ray_integration_max_itarations, c.sim.escape_radius,
                                           c.sim.ray_integration_step, rgb + (size_t)f * fbytes, &one);
       if (rc != CURVIS_OK) return rc;

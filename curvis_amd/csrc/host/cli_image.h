@@ -83,7 +83,12 @@ int image_main(const Args &a) {
     FILE *f = std::fopen(a.stats.c_str(), "w");
     if (f) {
       /* with a disc set the line carries n_disc: rays = n_pos + n_neg + n_none + n_disc */
-      const std::string disc_field = g_disc.set ? ", \"n_disc\": " + std::to_string(n_disc) : std::string();
+      std::string disc_field = g_disc.set ? ", \"n_disc\": " + std::to_string(n_disc) : std::string();
+      if (g_camera_velocity_set) { /* --camera-velocity: the line carries beta */
+        char buf[128];
+        std::snprintf(buf, sizeof buf, ", \"beta\": [%.17g, %.17g, %.17g]", g_camera_velocity[0], g_camera_velocity[1], g_camera_velocity[2]);
+        disc_field += buf;
+      }
       std::fprintf(f, "{\"frame\": 0, \"mode\": \"%s\", \"supersample\": %d, \"sky_filter\": \"%s\", \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu%s, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f}\n",
                    a.mode.c_str(), a.supersample, a.sky_filter ? "bilinear" : "nearest", (unsigned long long)st.rays, (unsigned long long)st.steps, (unsigned long long)st.n_pos,
                    (unsigned long long)st.n_neg, (unsigned long long)st.n_none, (unsigned long long)st.n_oob, disc_field.c_str(), st.kernel_ms,

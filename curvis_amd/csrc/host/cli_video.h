@@ -75,6 +75,32 @@ int video_main(const Args &a_in) {
     cams.push_back(cam);
   }
   const size_t n_frames = cams.size();
+  /* --camera-motion path: every frame's velocity from the poses of the frames before and after it -- the frame's time and its
+   * interpolated camera's (l, theta, phi); the ends repeat themselves.  A frame at the speed of light or beyond stops the run here. */
+  std::vector<double> betas;
+  if (a.camera_motion == "path") {
+    betas.resize(3 * n_frames);
+    auto pose = [&](size_t k, double *p) {
+      p[0] = times[k];
+      for (int i = 1; i < 4; ++i) p[i] = cams[k].pos[i];
+    };
+    for (size_t k = 0; k < n_frames; ++k) {
+      double prev[4], pos[4], next[4];
+      pose(k ? k - 1 : 0, prev);
+      pose(k, pos);
+      pose(k + 1 < n_frames ? k + 1 : k, next);
+      double *b = &betas[3 * k];
+      if (curvis_camera_path_velocity(&c.metric, prev, pos, next, a.light_speed, b) != CURVIS_OK)
+        die("Error in rendering video: --camera-motion path: invalid metric parameters");
+      const double b2 = (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2];
+      if (!(b2 < 1.0)) {
+        char buf[256];
+        std::snprintf(buf, sizeof buf, "Error in rendering video: --camera-motion path: frame %zu moves at %.6g times the speed of light "
+                                       "(beta = (%.6g, %.6g, %.6g), --light-speed %g)", k, std::sqrt(b2), b[0], b[1], b[2], a.light_speed);
+        die(buf);
+      }
+    }
+  }
   const size_t fbytes = (size_t)c.cam.resolution_x * c.cam.resolution_y * 3;
   std::mutex io_mu;
   std::atomic<int> failed{0};
@@ -370,7 +396,11 @@ int video_main(const Args &a_in) {
       std::vector<size_t> zoff;
       std::vector<uint32_t> zcrc;
       bool streams = false, have_crc = false; /* have_crc: the device also computed the PNG chunks' CRC-32 (two-pass front end) */
-      int rc = render_frames(ctx, a, c, bc.data(), (uint32_t)nb, c.sim.sampling_convergence_threshold_1, gpu_png ? nullptr : rgb_ptr, &st);
+      std::vector<double> bbeta; /* --camera-motion path: the velocities of this batch's frames */
+      if (!betas.empty())
+        for (size_t j = 0; j < nb; ++j) bbeta.insert(bbeta.end(), &betas[3 * b.frames[j]], &betas[3 * b.frames[j]] + 3);
+      int rc = render_frames(ctx, a, c, bc.data(), (uint32_t)nb, c.sim.sampling_convergence_threshold_1, gpu_png ? nullptr : rgb_ptr, &st,
+                             bbeta.empty() ? nullptr : bbeta.data());
       settle(); /* the previous batch's streams had this call to arrive under */
       if (rc == CURVIS_OK && gpu_png) {
         zoff.resize(nb + 1);
@@ -512,7 +542,12 @@ int video_main(const Args &a_in) {
             pr.first->frames += pr.second->frames;
           }
           std::printf("Rendering frame %zu/%zu...\n", k + 1, times.size());
-          const std::string disc_field = g_disc.set ? ", \"n_disc\": " + std::to_string((unsigned long long)fs_disc) : std::string();
+          std::string disc_field = g_disc.set ? ", \"n_disc\": " + std::to_string((unsigned long long)fs_disc) : std::string();
+          if (!betas.empty()) { /* --camera-motion path: the line carries the frame's beta */
+            char buf[128];
+            std::snprintf(buf, sizeof buf, ", \"beta\": [%.17g, %.17g, %.17g]", betas[3 * k], betas[3 * k + 1], betas[3 * k + 2]);
+            disc_field += buf;
+          }
           if (stats_f)
             std::fprintf(stats_f, "{\"frame\": %zu, \"time\": %.17g, \"device\": %d, \"mode\": \"%s\", \"supersample\": %d, \"sky_filter\": \"%s\", \"rays\": %llu, \"steps\": %llu, \"n_pos\": %llu, \"n_neg\": %llu, \"n_none\": %llu, \"n_oob\": %llu%s, \"kernel_ms\": %.4f, \"mray_steps_per_s\": %.1f, \"batch_frames\": %zu, \"batch_kernel_ms\": %.4f, \"batch_call_ms\": %.4f}\n",
                          k, times[k], device_of(rank), a.mode.c_str(), a.supersample, a.sky_filter ? "bilinear" : "nearest", (unsigned long long)fs.rays, (unsigned long long)fs.steps,

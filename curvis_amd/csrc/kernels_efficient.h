@@ -332,7 +332,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_kernel(const EfficientPix
     const unsigned off = P.tab_off[f], n = P.tab_n[f];
     double fin[3], space;
     cvk::efficient_pixel<true>(P.cams[f], P.frames[f], px, py, P.sx + off, P.m_e + off, P.c_e + off, P.m_s + off, P.c_s + off, n, fin, space,
-                               &P.recips, P.grid + P.grid_off[f], PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
+                               &P.recips, P.grid + P.grid_off[f], PROJ ? P.projection : cvk::PROJ_PERSPECTIVE, PROJ ? frame_boost(P.cams, P.n_frames, f) : nullptr);
     /* match escape_space { 1.0 => ..., -1.0 => ..., _ => black }.  One sky after the other, each under its own branch: the lanes of
      * a wave nearly always look at the same sky, and then its rotation, size and texel pointer are scalar operands of that one
      * pass -- selecting them per lane cost 22 v_cndmask and the VGPRs to hold the result */
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) void efficient_pixel_ss_kernel(const std::cond
     const unsigned off = P.tab_off[f], n = P.tab_n[f];
     double fin[3], space;
     cvk::efficient_pixel<true>(P.cams[f], P.frames[f], px, py, P.sx + off, P.m_e + off, P.c_e + off, P.m_s + off, P.c_s + off, n, fin, space,
-                               &P.recips, P.grid + P.grid_off[f], PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
+                               &P.recips, P.grid + P.grid_off[f], PROJ ? P.projection : cvk::PROJ_PERSPECTIVE, PROJ ? frame_boost(P.cams, P.n_frames, f) : nullptr);
     pos = (space == 1.0);
     neg = (space == -1.0);
     none = !(pos || neg);
@@ -491,11 +491,27 @@ struct DirectParamsAdapt : DirectParams { /* the ADAPT instantiations' argument:
   double kappa;
 };
 
+/* The argument of the PROJ = 1 forms: the other forms' with the frame's boost appended (cv_device.h camera_boost; read while P.projection
+ * carries PROJ_BOOSTED).  The PROJ = 0 forms keep their argument as it was. */
+template <class Base>
+struct WithCameraBoost : Base {
+  cvk::CameraBoost boost;
+};
+template <int ADAPT, int PROJ>
+using DirectArgsP = std::conditional_t<PROJ != 0, WithCameraBoost<std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>>,
+                                       std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>>;
+template <int ADAPT, int FILTER, int PROJ>
+using DirectArgs = std::conditional_t<FILTER == 2, WithSkyMip<DirectArgsP<ADAPT, PROJ>>, DirectArgsP<ADAPT, PROJ>>;
+template <int PROJ, class Args>
+__device__ __forceinline__ const cvk::CameraBoost *direct_boost(const Args &P) {
+  if constexpr (PROJ != 0) return &P.boost;
+  else return nullptr;
+}
+
 /* SS: supersampling factor (1, or 2 / 4 / 8: P.W x P.H and the camera are those of the fine grid, the epilogue averages) */
 template <int KIND, bool FAST, int SS = 1, int FILTER = 0, int PROJ = 0, int ADAPT = 0> /* FILTER: option "sky_filter", PROJ: option "projection", ADAPT: options "step_scale" (1) and "integrator" (2) */
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kind_has_log(KIND) ? 4 : 6)))
-void direct_kernel(const std::conditional_t<FILTER == 2, WithSkyMip<std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>>,
-                                            std::conditional_t<ADAPT != 0, DirectParamsAdapt, DirectParams>> P) {
+void direct_kernel(const DirectArgs<ADAPT, FILTER, PROJ> P) {
   [[maybe_unused]] unsigned texel_ss; /* supersampling: what the lane's ray saw, for the resolve after the branch */
   if constexpr (SS > 1) texel_ss = 0xFF000000u;
   [[maybe_unused]] unsigned which = 0u, Xc = 0u, Yc = 0u; /* FILTER = 2 (option "sky_mipmap"): the lane's sky (0: none) and its indices on it */
@@ -510,7 +526,7 @@ void direct_kernel(const std::conditional_t<FILTER == 2, WithSkyMip<std::conditi
   unsigned steps = 0, pos = 0, neg = 0, none = 0, oob = 0;
   if (valid) {
     double alpha, axis[3];
-    cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis, nullptr, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
+    cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis, nullptr, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE, direct_boost<PROJ>(P));
     double sa, ca;
     cv_sincos(alpha, &sa, &ca);
     const double p4[4] = {0.0, P.cam.pos[1], CV_PI / 2.0, 0.0};
@@ -532,7 +548,7 @@ void direct_kernel(const std::conditional_t<FILTER == 2, WithSkyMip<std::conditi
     unsigned texel = 0xFF000000u; /* NotEscaped / undefined tangent rotation: black */
     double angle;
     if (code != cvk::CODE_NONE && cvk::escape_angle_of<KIND>(M, q, angle)) {
-      cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis, nullptr, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE); /* again: not kept live across the loop */
+      cvk::efficient_pixel_geometry(P.cam, P.frame, px, py, alpha, axis, nullptr, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE, direct_boost<PROJ>(P)); /* again: not kept live across the loop */
       double fin[3];
       cvk::efficient_final_direction(P.frame, axis, angle, fin);
       const cvk::SkyParams &S = P.sky[code == cvk::CODE_POS ? 0 : 1];

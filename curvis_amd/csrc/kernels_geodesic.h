@@ -140,6 +140,12 @@ __device__ __forceinline__ bool decode_ray(const IntegrateParams &P, unsigned lo
   return px < P.W && py < P.H;
 }
 
+/* The moving camera (cv_device.h camera_boost): the CameraBoost of a launch's frames lie behind its cameras, n_frames of them after the
+ * n_frames CameraParams, while the launch's `projection` carries PROJ_BOOSTED (render_rays uploads them so); read under that bit only. */
+__device__ __forceinline__ const cvk::CameraBoost *frame_boost(const cvk::CameraParams *cams, unsigned n_frames, unsigned frame) {
+  return reinterpret_cast<const cvk::CameraBoost *>(cams + n_frames) + frame;
+}
+
 template <bool PHI>
 __device__ __forceinline__ void store_ray(const RayStore &S, size_t o, const cvk::Ray &q, unsigned steps, int code) {
   S.l[o] = q.l;
@@ -398,7 +404,8 @@ void geodesic_static(const IntegrateArgsD<ADAPT, FILTER, DISC> P) { /* the Heun 
   int code = cvk::CODE_NONE;
   [[maybe_unused]] double t = 0.0; /* ADAPT debug dump: x[0], the reference's t + (p_t g^tt) delta_k with p_t = 1, g^tt = -1 */
   if (id < P.total_rays && decode_ray(P, id, frame, px, py)) {
-    cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
+    if constexpr (PROJ != 0) cvk::ray_init<KIND, true>(M, P.cams[frame], px, py + P.row0, q, P.projection, frame_boost(P.cams, P.n_frames, frame));
+    else cvk::ray_init<KIND>(M, P.cams[frame], px, py + P.row0, q, PROJ ? P.projection : cvk::PROJ_PERSPECTIVE);
     if constexpr (ADAPT != 0 && PHI) t = P.cams[frame].pos[0];
     lane_ok_w = FAST && P.fast_ok && cvk::ray_fast_ok(q);
     valid = true;

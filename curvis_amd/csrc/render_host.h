@@ -125,6 +125,9 @@ struct curvis_ctx {
   int last_pixel_tiled = 0; /* the efficient renderer's last per-pixel launch: 0 efficient_pixel_kernel (linear), 1 the tile-enumerating one */
   int projection = 0;       /* 0: the reference's perspective camera; 1: equirectangular; 2: equidistant fisheye -- pixel -> camera-space
                                vector, defined in include/curvis_hip.h (cv_device.h camera_pixel_vector) */
+  std::vector<double> cam_beta; /* curvis_ctx_set_camera_velocities: (b_l, b_theta, b_phi) per triple, validated when set; empty: every
+                                   camera is static.  One triple serves every frame of a call, n triples a call of n frames
+                                   (prepare_camera_boost) */
   int integrator = 0;       /* 0: forward Euler, the reference's loop; 1: Heun's method composed of two Euler steps -- defined in
                                include/curvis_hip.h (cv_device.h ray_step_heun) */
   int64_t step_scale = 0;   /* S in [0, 2^20]; 0: every Euler step takes the call's delta (the reference).  S != 0: L0 = S / 256, and a step
@@ -262,7 +265,8 @@ constexpr uint32_t kSkyFilterMaxSide = 1u << 23;
  * -- ss > 1 -- the cameras of the call over the ss times finer grid: the same sensor at ss times the resolution (pixel (ss x, ss y)
  * of it is pixel (x, y) of the original, cv_device.h ray_init). */
 struct CallShape {
-  uint32_t ss = 1, filter = 0, projection = 0;
+  uint32_t ss = 1, filter = 0, projection = 0; /* projection: the option's value, with cvk::PROJ_BOOSTED on top while a frame of the call moves */
+  std::vector<cvk::CameraBoost> boost;         /* then: one per frame (a frame at rest has B = 0), else empty */
   double kappa = 0.0; /* option "step_scale" != 0: RN(delta / L0), else +0 (read under "integrator" = 1 only: step_delta then gives delta) */
   int adapt = 0;      /* the kernels' ADAPT: 2 option "integrator" = 1, else 1 option "step_scale" != 0, else 0 */
   std::vector<curvis_camera> fine;
@@ -287,6 +291,31 @@ int step_scale_kappa(curvis_ctx *ctx, double delta, double &kappa, int &adapt) {
   if (ctx->step_scale != 0) kappa = cvk::step_kappa(delta, ctx->step_scale);
   return CURVIS_OK;
 }
+/* The moving camera (curvis_ctx_set_camera_velocities) for a call of n_frames frames: which triple serves which frame, and the five
+ * doubles of every frame from its own rot (cv_device.h camera_boost_prepare).  A call none of whose frames moves keeps an empty
+ * s.boost and is the call it would be with the velocities cleared. */
+int prepare_camera_boost(curvis_ctx *ctx, const curvis_camera *cams, uint32_t n_frames, CallShape &s) {
+  s.boost.clear();
+  const size_t n = ctx->cam_beta.size() / 3;
+  if (n == 0) return CURVIS_OK;
+  if (n != 1 && n != n_frames)
+    return fail(ctx, CURVIS_E_INVALID, "camera velocity: " + std::to_string(n) + " velocities are set for a call of " + std::to_string(n_frames) +
+                                           " frame(s) (set one for all frames, one per frame, or none)");
+  std::vector<cvk::CameraBoost> K(n_frames);
+  bool moving = false;
+  for (uint32_t f = 0; f < n_frames; ++f) {
+    const int rc = cvk::camera_boost_prepare(cams[f].rot, &ctx->cam_beta[n == 1 ? 0 : 3 * (size_t)f], K[f]);
+    if (rc < 0) return fail(ctx, CURVIS_E_INVALID, "camera velocity: the speed of frame " + std::to_string(f) + " in its camera's frame is not below 1 (the speed of light)");
+    moving = moving || rc > 0;
+  }
+  if (moving) s.boost.swap(K);
+  return CURVIS_OK;
+}
+/* the cameras of a call as the kernels read them: n CameraParams and, while a frame moves, the n CameraBoost behind them
+ * (kernels_geodesic.h frame_boost) */
+size_t staged_cameras_bytes(uint32_t n, const cvk::CameraBoost *boost) { return (sizeof(cvk::CameraParams) + (boost ? sizeof(cvk::CameraBoost) : 0)) * (size_t)n; }
+void stage_cameras(unsigned char *dst, const curvis_camera *cams, uint32_t n, const cvk::CameraBoost *boost);
+
 /* cams: the caller's n_frames cameras on entry, those the kernels run over on return (s.fine with ss > 1).  With the filter on, both
  * skies must be small enough for it; a fisheye whose image corner lies beyond the angle pi from the axis is refused; too_large is the renderer's message for a fine resolution that no longer fits 32 bits. */
 int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_frames, double delta, const char *too_large, CallShape &s) {
@@ -302,12 +331,14 @@ int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_f
       if (sky.texels && (sky.w > kSkyFilterMaxSide || sky.h > kSkyFilterMaxSide))
         return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: a sky of more than 2^23 texels per side (256 times its size must fit 32 bits)");
   s.projection = (uint32_t)ctx->projection;
+  if (int rc = prepare_camera_boost(ctx, cams, n_frames, s)) return rc;
   if (s.projection == (uint32_t)cvk::PROJ_FISHEYE)
     for (uint32_t f = 0; f < n_frames; ++f) {
       const curvis_camera &c = cams[f];
       if (!(0.5 * std::sqrt(c.sensor_w * c.sensor_w + c.sensor_h * c.sensor_h) / c.focal <= CV_PI))
         return fail(ctx, CURVIS_E_INVALID, "projection = 2 (fisheye): half the sensor's diagonal over the focal length exceeds pi");
     }
+  if (!s.boost.empty()) s.projection |= (uint32_t)cvk::PROJ_BOOSTED;
   if (s.ss <= 1u) return CURVIS_OK;
   s.fine.assign(cams, cams + n_frames);
   for (curvis_camera &c : s.fine) {
@@ -472,6 +503,14 @@ cvk::CameraParams make_camera(const curvis_camera &c) {
   C.res_x = (double)c.res_x;
   C.res_y = (double)c.res_y;
   return C;
+}
+
+void stage_cameras(unsigned char *dst, const curvis_camera *cams, uint32_t n, const cvk::CameraBoost *boost) {
+  for (uint32_t f = 0; f < n; ++f) {
+    const cvk::CameraParams C = make_camera(cams[f]);
+    std::memcpy(dst + sizeof C * f, &C, sizeof C);
+  }
+  if (boost) std::memcpy(dst + sizeof(cvk::CameraParams) * n, boost, sizeof(cvk::CameraBoost) * n);
 }
 
 cvk::SkyParams make_sky_params(const curvis_ctx *ctx, int k) {
@@ -731,7 +770,8 @@ struct BruteCall {
   uint32_t ss;                   /* supersampling factor.  With ss > 1 the cameras, the band, W and H are those of the ss times finer
                                     RAY grid (what the kernels run over); npix and fb_bytes are always those of the frames written */
   uint32_t filter;               /* option "sky_filter" for this call */
-  uint32_t projection;           /* option "projection" for this call */
+  uint32_t projection;           /* option "projection" for this call (CallShape: with PROJ_BOOSTED while a frame moves) */
+  const cvk::CameraBoost *boost = nullptr; /* ... and then the frames' boosts, n_frames of them */
   double kappa = 0.0;            /* option "step_scale" for this call: RN(delta / L0) ... */
   int adapt = 0;                 /* ... and the kernels' ADAPT (CallShape) */
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
@@ -773,7 +813,8 @@ RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
    * the others, a pattern the hand-over was never tuned on).  Option "integrator" = 1 likewise: there is no relay form of the Heun step.  Option "sky_mipmap" = 1: no relay
    * form either (the epilogue is not where a single frame's time goes) */
   /* a disc: the static kernel too -- there is no relay form of the DISC kernels */
-  p.relay = !ctx->disc_set && c.metric->kind != CURVIS_METRIC_SCHWARZSCHILD && !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
+  /* a moving camera: the static kernel as well (render_impl) */
+  p.relay = !c.boost && !ctx->disc_set && c.metric->kind != CURVIS_METRIC_SCHWARZSCHILD && !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
             relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
   p.chunk = c.n_frames;
   p.store_bytes = p.relay ? relay_staging : 0;
@@ -823,6 +864,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   P.refill_threshold = ctx->refill_threshold < 1 ? 1 : (ctx->refill_threshold > 64 ? 64 : ctx->refill_threshold);
   P.fast_ok = cvk::metric_fast_ok(c.metric->kind, MP, c.max_radius) ? 1 : 0;
   P.projection = (int)c.projection;
+  if (c.boost && (f0 != 0 || nf != c.n_frames)) return fail(ctx, CURVIS_E_INVALID, "camera velocity: the frames' boosts lie behind the cameras of the whole call, which one fused launch renders");
   P.kappa = c.kappa;
   P.t_out = (c.adapt && c.dbg_out) ? ctx->d_dbg_t + (size_t)f0 * c.npix : nullptr;
   /* diagnostics only (CURVIS_TRACE_FILE): per-wave records of this launch, binary u64 x 4 per wave */
@@ -1076,10 +1118,12 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
   if (c.dbg_out && c.adapt && (rc = ctx->d_dbg_t.reserve(ctx, c.npix * c.n_frames))) return rc;
   const RenderPath path = choose_render_path(ctx, c);
   if (path.store_bytes && (rc = ctx->d_store.reserve(ctx, path.store_bytes))) return rc;
-  if ((rc = ctx->d_cams.reserve(ctx, c.n_frames))) return rc;
-  if ((rc = ctx->h_cams.reserve(ctx, c.n_frames))) return rc;
-  for (uint32_t f = 0; f < c.n_frames; ++f) ctx->h_cams[f] = make_camera(c.cams[f]);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, sizeof(cvk::CameraParams) * c.n_frames, hipMemcpyHostToDevice, ctx->stream));
+  const size_t cams_bytes = staged_cameras_bytes(c.n_frames, c.boost);
+  const size_t cams_slots = (cams_bytes + sizeof(cvk::CameraParams) - 1) / sizeof(cvk::CameraParams); /* with the boosts behind the cameras */
+  if ((rc = ctx->d_cams.reserve(ctx, cams_slots))) return rc;
+  if ((rc = ctx->h_cams.reserve(ctx, cams_slots))) return rc;
+  stage_cameras(reinterpret_cast<unsigned char *>(ctx->h_cams.p), c.cams, c.n_frames, c.boost);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cams, ctx->h_cams, cams_bytes, hipMemcpyHostToDevice, ctx->stream));
 
   const cvk::MetricParams MP = make_metric(*c.metric);
   if (ctx->disc_set && ctx->disc_motion != 0) { /* the camera's half of the emission shift, once per frame, by the one shared function */
@@ -1142,7 +1186,19 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
     if (ctx->disc_motion != 0 && metric && metric->kind != CURVIS_METRIC_SCHWARZSCHILD)
       return fail(ctx, CURVIS_E_INVALID, "the disc motion is Keplerian and needs the Schwarzschild metric: in the other kinds g00 = -1, free matter is at rest and nothing orbits (set the motion to 0: curvis_ctx_set_disc_motion)");
   }
-  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->sky_mipmap && !ctx->projection && !ctx->step_scale && !ctx->integrator)) return render_rays(ctx, c);
+  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->sky_mipmap && !ctx->projection && !ctx->step_scale && !ctx->integrator && ctx->cam_beta.empty())) return render_rays(ctx, c);
+  /* a moving camera (curvis_ctx_set_camera_velocities) lives in the prologue of the fused static kernel, like the projections: the same
+   * three shapes are refused, under its name and before the others, while a frame of the call moves; and the disc's emission shift takes
+   * the camera to be at rest (include/curvis_hip.h), so a disc with a motion refuses the call too */
+  CallShape shape;
+  if (int rc = prepare_camera_boost(ctx, cams, n_frames, shape)) return rc;
+  if (!shape.boost.empty()) {
+    if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "camera velocity: the debug dump replays the static camera (clear the velocities: curvis_ctx_set_camera_velocities with n = 0)");
+    if (ctx->variant == 0) return fail(ctx, CURVIS_E_INVALID, "camera velocity: variant = 0 (the persistent kernel) has the static camera only");
+    if (ctx->fuse_shade == 0) return fail(ctx, CURVIS_E_INVALID, "camera velocity: fuse_shade = 0 (the unfused static kernel) has the static camera only");
+    if (ctx->disc_set && ctx->disc_motion != 0)
+      return fail(ctx, CURVIS_E_INVALID, "camera velocity: the emission shift of a moving disc takes the camera to be at rest (set the disc's motion to 0, or clear the velocities)");
+  }
   /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under
    * the name of the projection when it is on, else of the filter when that is on, else of the supersampling when that is on.  The scaled
    * steps (option "step_scale") exist in the fused kernels and in the debug dump's: a shape with a message of its own in the last
@@ -1178,8 +1234,8 @@ int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camer
       if (!why && h) why = s.integrator;
       if (why) return fail(ctx, CURVIS_E_INVALID, why);
     }
-  CallShape shape;
   if (int rc = prepare_call_shape(ctx, c.cams, n_frames, delta, "frame or batch too large", shape)) return rc;
+  c.boost = shape.boost.empty() ? nullptr : shape.boost.data();
   c.kappa = shape.kappa;
   c.adapt = shape.adapt;
   c.ss = shape.ss;

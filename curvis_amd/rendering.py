@@ -115,6 +115,18 @@ def render_image_sharded(context, metric, camera, max_iterations, max_radius, de
     return np.concatenate([p[1] for p in parts], axis=0), [p[0] for p in parts]
 
 
+def check_camera_motion(camera_motion, light_speed):
+    """camera_motion is "static" (the reference's camera) or "path"; light_speed a positive finite number; ValueError otherwise"""
+    if not isinstance(camera_motion, str) or camera_motion not in ("static", "path"):
+        raise ValueError("camera_motion must be 'static' or 'path'")
+    try:
+        c = float(light_speed)
+    except (TypeError, ValueError):
+        c = 0.0
+    if not (c > 0.0 and c < float("inf")):
+        raise ValueError("light_speed must be a positive number")
+
+
 def check_disc_mode(disc, mode, metric=None):
     """an accretion disc (curvis_amd.Disc) lives in the per-pixel renderer alone: ValueError for anything but a Disc or None, and for a
     Disc with a mode other than "brute" -- there is no silent change of mode; and for a Disc with a motion under a metric that is not
@@ -152,12 +164,14 @@ class ImageRenderingSystem:
     reference; "euler" is its loop) integrates with Heun's method, two Euler steps averaged (library option "integrator");
     sky_mipmap=True (not in the reference; needs sky_filter="bilinear") takes the blend on a mip pyramid of the sky (library option
     "sky_mipmap"); disc=Disc(...) (not in the reference) puts an accretion disc into the equatorial plane, which only mode="brute"
-    can see: any other mode raises ValueError."""
+    can see: any other mode raises ValueError; velocity=(b_l, b_theta, b_phi) (not in the reference; None is its static camera)
+    renders the aberrated view of a camera that moves with that velocity, in units of c (Context.set_camera_velocities)."""
 
     def __init__(self, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-                 projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
+                 projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None, velocity=None):
         from .images import load_image_as_spherical_image
-        from .systems import RelativisticSystem, check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
+        from .systems import RelativisticSystem, check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, check_velocity
+        self.velocity = check_velocity(velocity)
         check_disc_mode(disc, mode, metric)
         check_step_scale(step_scale)
         self.step_scale = step_scale
@@ -181,10 +195,10 @@ class ImageRenderingSystem:
 
     @classmethod
     def new(cls, metric, image_rendering_settings, context=None, mode="efficient", supersample=1, sky_filter="nearest",
-            projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
+            projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None, velocity=None):
         """ImageRenderingSystem::new(metric, image_rendering_settings) (src/rendering.rs:33-70)"""
         return cls(metric, image_rendering_settings, context=context, mode=mode, supersample=supersample, sky_filter=sky_filter,
-                   projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap, disc=disc)
+                   projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap, disc=disc, velocity=velocity)
 
     def render(self):
         import os
@@ -200,13 +214,13 @@ class ImageRenderingSystem:
             image = self.relativistic_system.render_image(st.max_iterations_propagation, st.escape_radius, st.ray_integration_step,
                                                           supersample=self.supersample, sky_filter=self.sky_filter,
                                                           projection=self.projection, step_scale=self.step_scale,
-                                                          integrator=self.integrator, sky_mipmap=self.sky_mipmap)
+                                                          integrator=self.integrator, sky_mipmap=self.sky_mipmap, velocity=self.velocity)
         else:
             image = self.relativistic_system.render_image_efficient(
                 st.max_iterations_propagation, st.escape_radius, st.ray_integration_step, st.alphas_num,
                 st.max_iterations_sampling, st.sampling_convergence_threshold_1, st.sampling_convergence_threshold_2,
                 supersample=self.supersample, sky_filter=self.sky_filter, projection=self.projection, step_scale=self.step_scale,
-                integrator=self.integrator, sky_mipmap=self.sky_mipmap)
+                integrator=self.integrator, sky_mipmap=self.sky_mipmap, velocity=self.velocity)
         path_of_image = os.path.join(folder, os.path.splitext(st.output_image_name)[0] + ".png")
         save_image(path_of_image, image)
         return path_of_image
@@ -240,13 +254,20 @@ class VideoRenderingSystem:
     needs sky_filter="bilinear"): library option "sky_mipmap" on every frame -- the blend on a mip pyramid of the sky, which lowers the
     frame-to-frame flicker of the strongly minified secondary images (measured in profiles/sky_mipmap_quality.txt).  disc=Disc(...) (not
     in the reference): an accretion disc in the equatorial plane on every frame; it needs mode="brute" (ValueError otherwise), and the
-    per-frame statistics then carry n_disc, the rays that ended on it (rays = n_pos + n_neg + n_none + n_disc)."""
+    per-frame statistics then carry n_disc, the rays that ended on it (rays = n_pos + n_neg + n_none + n_disc).
+    camera_motion="path" (not in the reference; "static" is its camera, which stands still at every frame's pose): every frame is the
+    aberrated view of a camera that moves along the path -- its velocity is curvis_camera_path_velocity of the interpolated poses of
+    the frames before and after it, with light_speed path units per unit of path time (1.0 by default); a frame whose speed is c or
+    more raises ValueError before anything is rendered, and the per-frame statistics carry beta.  Aberration only: no Doppler shift."""
 
     def __init__(self, metric, context, interpolator, frame_rate, resolution, camera_diagonal, camera_focal_length,
                  escape_radius, max_iterations_propagation, ray_integration_step, rank=0, world_size=1, batch=8,
                  mode="efficient", sampling_initial_nums=100, sampling_convergence_threshold_1=1e-5, supersample=1,
-                 sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
+                 sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None,
+                 camera_motion="static", light_speed=1.0):
         from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample
+        check_camera_motion(camera_motion, light_speed)
+        self.camera_motion, self.light_speed = camera_motion, float(light_speed)
         check_disc_mode(disc, mode, metric)
         self.disc = disc
         self._step_scale = check_step_scale(step_scale)
@@ -279,7 +300,8 @@ class VideoRenderingSystem:
 
     @classmethod
     def new(cls, metric, video_rendering_settings, context=None, rank=0, world_size=1, batch=8, mode="efficient", supersample=1,
-            sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None):
+            sky_filter="nearest", projection="perspective", step_scale=0.0, integrator="euler", sky_mipmap=False, disc=None,
+            camera_motion="static", light_speed=1.0):
         """VideoRenderingSystem::new(metric, video_rendering_settings) (src/rendering.rs:188-221): loads the two
         backgrounds into the context's HBM and the camera path into an Interpolator.  The reference passes
         `alphas_num` and `max_iterations_sampling` separately and `sampling_convergence_threshold_1` twice (:299-307);
@@ -287,6 +309,7 @@ class VideoRenderingSystem:
         from .images import load_image_as_spherical_image
         from .systems import check_sky_mipmap, check_integrator, check_projection, check_sky_filter, check_step_scale, check_supersample, default_context, SchwarzschildMetric, black_sky
         check_supersample(supersample)  # before the context and the files are touched
+        check_camera_motion(camera_motion, light_speed)
         check_disc_mode(disc, mode, metric)
         check_sky_mipmap(sky_mipmap)
         check_step_scale(step_scale)
@@ -306,7 +329,7 @@ class VideoRenderingSystem:
                    mode=mode, sampling_initial_nums=st.alphas_num,
                    sampling_convergence_threshold_1=st.sampling_convergence_threshold_1, supersample=supersample,
                    sky_filter=sky_filter, projection=projection, step_scale=step_scale, integrator=integrator, sky_mipmap=sky_mipmap,
-                   disc=disc)
+                   disc=disc, camera_motion=camera_motion, light_speed=light_speed)
         self.max_iterations_sampling = int(st.max_iterations_sampling)
         self.video_rendering_settings = st
         return self
@@ -360,7 +383,30 @@ class VideoRenderingSystem:
         return Camera(it.camera_position(t), it.camera_forward(t), it.camera_up(t), self.camera_focal_length,
                       self.camera_diagonal, self.resolution[0], self.resolution[1])
 
-    def _render_batch(self, cams, download):
+    def frame_velocities(self, times, frames):
+        """camera_motion="path": the velocity of every frame of `frames` (indices into `times`), from the poses of the frames before
+        and after it; ValueError for a speed of c or more, naming the frame.  None under "static"."""
+        if getattr(self, "camera_motion", "static") != "path":
+            return None
+        from .systems import camera_path_velocity
+        it = self.interpolator
+        def pose(k):  # (the frame's time, then l, theta, phi of the frame's interpolated camera); the ends repeat themselves
+            t = times[min(max(k, 0), len(times) - 1)]
+            return np.concatenate(([t], it.camera_position(t)[1:4]))
+        out = {}
+        for k in frames:
+            b = camera_path_velocity(self.metric, pose(k - 1), pose(k), pose(k + 1), self.light_speed)
+            if not (b[0] * b[0] + b[1] * b[1] + b[2] * b[2] < 1.0):
+                raise ValueError("camera_motion='path': frame %d moves at %.6g times the speed of light (beta = (%.6g, %.6g, %.6g), light_speed = %g)"
+                                 % (k, (b[0] * b[0] + b[1] * b[1] + b[2] * b[2]) ** 0.5, b[0], b[1], b[2], self.light_speed))
+            out[k] = b
+        return out
+
+    def _render_batch(self, cams, download, velocities=None):
+        if velocities is not None:  # set around the render call, as the options are
+            from .systems import _CameraVelocities
+            with _CameraVelocities(self.context, velocities):
+                return self._render_batch(cams, download)
         if (getattr(self, "supersample", 1) != 1 or getattr(self, "_sky_filter", 0) != 0 or getattr(self, "_projection", 0) != 0
                 or getattr(self, "_step_scale", 0) != 0 or getattr(self, "_integrator", 0) != 0 or getattr(self, "_sky_mipmap", 0) != 0):
             from .systems import _Supersampled
@@ -407,6 +453,7 @@ class VideoRenderingSystem:
         times = self.times_of_frames()
         mine = frames_of_rank(len(times), self.rank, self.world_size)
         out = []
+        beta = self.frame_velocities(times, mine)  # before anything is rendered
         disc = self.disc
         # the context's disc is this system's, None included (a context shared between systems must not leak one); a context without the
         # entry point, such as the tests' stubs, never had one to remove
@@ -420,7 +467,7 @@ class VideoRenderingSystem:
             cams = nxt
             nxt = cams_of(batches[bi + 1]) if bi + 1 < len(batches) else None
             self._prefetch(nxt)
-            rgb, st = self._render_batch(cams, download and not streams)
+            rgb, st = self._render_batch(cams, download and not streams, [beta[k] for k in idx] if beta is not None else None)
             frames = list(rgb) if (download and not streams) else [None] * len(cams)
             per = self.context.frame_stats()
             if streams:
@@ -436,6 +483,8 @@ class VideoRenderingSystem:
                          rays=int(s.rays), steps=int(s.steps), n_pos=int(s.n_pos), n_neg=int(s.n_neg),
                          n_none=int(s.n_none), n_oob=int(s.n_oob), kernel_ms=float(s.kernel_ms),
                          batch_kernel_ms=float(st.kernel_ms))
+                if beta is not None:
+                    d["beta"] = beta[k]
                 if disc is not None:  # a ray may have ended on the disc: rays = n_pos + n_neg + n_none + n_disc
                     d["n_disc"] = self.context.frame_disc_hits(len(out) - done_before)
                 out.append(d)

@@ -457,6 +457,23 @@ class Context:
         except _abi.CurvisError as e:
             raise ValueError(str(e)) from None
 
+    def set_camera_velocities(self, velocities):
+        """curvis_ctx_set_camera_velocities: None (or an empty sequence) clears them; one (b_l, b_theta, b_phi) serves every frame of a
+        render call, n of them a call of n frames.  In units of c, as the static observer at the camera measures them, in the frame
+        the camera's forward and up live in.  ValueError for a speed that is not below 1.  Aberration only: no Doppler shift, no beaming."""
+        if velocities is None or len(velocities) == 0:
+            check(lib().curvis_ctx_set_camera_velocities(self._h, None, 0), self._h)
+            return
+        beta = np.ascontiguousarray(velocities, dtype=np.float64)
+        if beta.ndim == 1:
+            beta = beta.reshape(1, -1)
+        if beta.ndim != 2 or beta.shape[1] != 3:
+            raise ValueError("camera velocities: one (b_l, b_theta, b_phi) per frame")
+        try:
+            check(lib().curvis_ctx_set_camera_velocities(self._h, beta.ctypes.data_as(C.POINTER(C.c_double)), beta.shape[0]), self._h)
+        except _abi.CurvisError as e:
+            raise ValueError(str(e)) from None
+
     def frame_disc_hits(self, frame=None):
         """rays that ended on the disc in one frame (or the list for all frames) of the last render call (curvis_ctx_frame_disc_hits)"""
         def one(k):
@@ -982,6 +999,48 @@ class _Supersampled:
         return False
 
 
+def check_velocity(velocity):
+    """a camera velocity as three floats, or None: (b_l, b_theta, b_phi) in units of c; ValueError for anything else and for a speed
+    that is not below 1"""
+    if velocity is None:
+        return None
+    try:
+        b = tuple(float(v) for v in velocity)
+    except (TypeError, ValueError):
+        b = ()
+    if len(b) != 3 or not (b[0] * b[0] + b[1] * b[1] + b[2] * b[2] < 1.0):
+        raise ValueError("velocity must be (b_l, b_theta, b_phi) with a speed below 1 (the speed of light)")
+    return b
+
+
+class _CameraVelocities:
+    """the context's camera velocities set to `velocities` (None: cleared) for the duration of a render call, then cleared"""
+
+    def __init__(self, context, velocities):
+        self.context, self.velocities = context, velocities
+
+    def __enter__(self):
+        self.context.set_camera_velocities(self.velocities)
+
+    def __exit__(self, *exc):
+        if self.velocities is not None:
+            self.context.set_camera_velocities(None)
+        return False
+
+
+def camera_path_velocity(metric, pos_prev, pos, pos_next, light_speed=1.0):
+    """curvis_camera_path_velocity: the velocity (b_l, b_theta, b_phi) of a camera at pose pos = (t, l, theta, phi) between the poses
+    before and after it (the first frame of a path passes pos_prev = pos, the last pos_next = pos).  Angle differences are taken as
+    they are: unwrap a path whose phi jumps by 2 pi."""
+    a, b, c = (np.ascontiguousarray(p, dtype=np.float64) for p in (pos_prev, pos, pos_next))
+    out = np.zeros(3, dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    m = metric._c()
+    check(lib().curvis_camera_path_velocity(C.byref(m), a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp),
+                                            float(light_speed), out.ctypes.data_as(dp)), None)
+    return tuple(out)
+
+
 class RelativisticSystem:
     """RelativisticSystem<M> (src/systems.rs:68-73).  The three renderers take supersample=N (1, 2, 4 or 8; not in the
     reference): N x N rays per pixel, averaged on the device into the camera's resolution; and sky_filter="nearest" (the
@@ -992,6 +1051,8 @@ class RelativisticSystem:
     forward Euler) or "heun" (not in the reference: Heun's method, second order, two Euler steps averaged; library option
     "integrator"); and sky_mipmap (False or True; not in the reference: with sky_filter="bilinear", the blend is taken on a mip
     pyramid of the sky at the level of the ray's footprint among its neighbours; library option "sky_mipmap").
+    velocity=(b_l, b_theta, b_phi) (not in the reference; None, the default, is its static camera): the camera moves with that
+    velocity, in units of c, and the frame shows the aberrated view (Context.set_camera_velocities; no Doppler shift, no beaming).
     disc (a Disc or None; not in the reference): an accretion disc in the equatorial plane, seen by render_image with every keyword;
     render_image_efficient, render_image_direct and render_image_debug raise ValueError while it is set."""
 
@@ -1023,12 +1084,12 @@ class RelativisticSystem:
             raise ValueError("a disc is set: %s cannot see it -- render_image (the per-pixel renderer) does" % what)
 
     def render_image(self, max_iterations, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
-                     step_scale=0.0, integrator="euler", sky_mipmap=False):
+                     step_scale=0.0, integrator="euler", sky_mipmap=False, velocity=None):
         """The per-pixel renderer; returns an HxWx3 uint8 array (DynamicImage::ImageRgb8)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip), _CameraVelocities(self.context, check_velocity(velocity)):
             rgb, st = self.context.render_brute(self.metric, self.camera, max_iterations, max_radius, delta)
         self.last_stats = st
         return rgb
@@ -1036,13 +1097,13 @@ class RelativisticSystem:
     def render_image_efficient(self, max_iterations_propagation, max_radius, delta, alpha_nums,
                                max_iterations_sampling, sampling_convergence_threshold_1,
                                sampling_convergence_threshold_2, supersample=1, sky_filter="nearest", projection="perspective",
-                               step_scale=0.0, integrator="euler", sky_mipmap=False):
+                               step_scale=0.0, integrator="euler", sky_mipmap=False, velocity=None):
         """src/systems.rs:333-343: the renderer behind `curvis image` / `curvis video`."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
         self._refuse_disc("render_image_efficient reduces every ray to an equatorial orbit and")
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip), _CameraVelocities(self.context, check_velocity(velocity)):
             rgb, st = self.context.render_efficient(self.metric, self.camera, max_iterations_propagation, max_radius, delta,
                                                     alpha_nums, max_iterations_sampling, sampling_convergence_threshold_1,
                                                     sampling_convergence_threshold_2)
@@ -1050,14 +1111,14 @@ class RelativisticSystem:
         return rgb
 
     def render_image_direct(self, max_iterations_propagation, max_radius, delta, supersample=1, sky_filter="nearest", projection="perspective",
-                            step_scale=0.0, integrator="euler", sky_mipmap=False):
+                            step_scale=0.0, integrator="euler", sky_mipmap=False, velocity=None):
         """NOT in the reference: the image render_image_efficient approximates, with compute_escape_angle evaluated
         for every pixel instead of sampled and interpolated (a quality option; Context.render_direct)."""
         factor, filt, proj = check_supersample(supersample), check_sky_filter(sky_filter), check_projection(projection)
         scale, heun, mip = check_step_scale(step_scale), check_integrator(integrator), check_sky_mipmap(sky_mipmap)
         self._refuse_disc("render_image_direct reduces every ray to an equatorial orbit and")
         self._bind_skies()
-        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip):
+        with _Supersampled(self.context, factor, filt, proj, scale, heun, mip), _CameraVelocities(self.context, check_velocity(velocity)):
             rgb, st = self.context.render_direct(self.metric, self.camera, max_iterations_propagation, max_radius, delta)
         self.last_stats = st
         return rgb

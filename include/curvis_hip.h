@@ -336,6 +336,56 @@ int curvis_camera_outward_vector(const curvis_camera *camera, uint32_t px, uint3
  * range check is made by the render calls, not here. */
 int curvis_camera_outward_vector_projected(const curvis_camera *camera, int32_t projection, uint32_t px, uint32_t py,
                                            double camera_space[3], double world_space[3]);
+/* The moving camera (not in the reference, whose cameras are static observers): relativistic aberration.  A frame may be given the
+ * velocity beta = (b_l, b_theta, b_phi) of its camera: the components, in units of c, that the static observer at the camera's position
+ * measures, in the tangent frame `forward` and `up` live in (camera.rot maps camera space into it).  For the Schwarzschild kind, whose
+ * rays are those of the optical metric, beta is the optical-metric speed with respect to coordinate time; conformal invariance keeps
+ * everything below unchanged.  A pixel then looks along the direction the static observer assigns to what the moving camera sees along
+ * that pixel.  Every operation is one individually rounded FP64 operation in the order written, without contraction; square roots and
+ * quotients are the correctly rounded IEEE ones.
+ * Once per frame (curvis_camera_boost_prepare; rot[r][i] = camera.rot[3 r + i]):
+ *   1. c_i = ((rot[0][i] b_l) + rot[1][i] b_theta) + rot[2][i] b_phi for i = 0, 1, 2: the camera-space velocity.
+ *   2. b2 = (c_0 c_0 + c_1 c_1) + c_2 c_2.
+ *   3. b2 == 0: the frame is not boosted; its pixels are those of a call without a velocity, bit for bit.
+ *   4. !(b2 < 1.0), a NaN included: CURVIS_E_INVALID.
+ *   5. b = sqrt(b2), g = 1.0 / sqrt(1.0 - b2), u_i = c_i / b, A = g - 1.0, B = g b.
+ * Per ray, with vec = (x, y, z) the un-normalised camera-space vector of the pixel under the call's "projection":
+ *   1. n = sqrt((x x + y y) + z z).
+ *   2. p = (x u_0 + y u_1) + z u_2.
+ *   3. s = A p - B n.
+ *   4. vec' = (x + u_0 s, y + u_1 s, z + u_2 s).
+ * The reference's sequence (normalize, the rotation, new_photon) continues with vec'.  Up to that normalisation vec' is
+ * (gamma (d_par - beta), d_perp) for a pixel that looks along d in the camera's rest frame: cos theta_static = (cos theta' - beta) /
+ * (1 - beta cos theta').  Both functions are one text for host and device (cv_device.h camera_boost_prepare, camera_boost).
+ * This is aberration and nothing else: no Doppler shift and no beaming of the sky, no light-travel-time effect, no acceleration, and
+ * the camera's motion does not enter the emission shift of a moving disc.
+ *
+ * curvis_ctx_set_camera_velocities: beta holds 3 n doubles, one triple per frame; n = 0 or beta = NULL clears them.  The state belongs
+ * to the context and stays until it is set again.  CURVIS_E_INVALID (the former state stays) for a triple whose own
+ * (b_l b_l + b_theta b_theta) + b_phi b_phi is not below 1.  A render call of F frames -- every renderer: curvis_render_brute, _rows,
+ * _batch, curvis_render_efficient, _batch, curvis_render_direct -- takes triple f for its frame f when n == F, the one triple for every
+ * frame when n == 1, and is refused with CURVIS_E_INVALID, rendering nothing, for any other n != 0.  Steps 1-5 run at call time with
+ * each frame's own rot.  It works with every metric kind and every option, and with a disc whose motion is 0.  While a frame of the
+ * call moves, curvis_render_brute_debug, "variant" = 0, "fuse_shade" = 0 and a disc with a motion other than 0 are refused under the
+ * name "camera velocity", and the brute renderer takes the static kernel.  With the velocities cleared, or all of them zero, every
+ * call launches the kernels it launched before. */
+int curvis_ctx_set_camera_velocities(curvis_ctx *ctx, const double *beta, uint32_t n);
+/* Steps 1-5 above on the host (no GPU needed): out = (u_0, u_1, u_2, A, B), all zeros for a frame that is not boosted (a boosted one has
+ * B > 0).  CURVIS_E_INVALID for a null pointer or step 4. */
+int curvis_camera_boost_prepare(const curvis_camera *camera, const double beta[3], double out[5]);
+/* curvis_camera_outward_vector_projected for a camera with velocity beta: vec' through the reference's normalize, and its rotation into
+ * world space; either output may be NULL.  beta = 0 gives that function's bits. */
+int curvis_camera_outward_vector_boosted(const curvis_camera *camera, int32_t projection, const double beta[3], uint32_t px, uint32_t py,
+                                         double camera_space[3], double world_space[3]);
+/* The velocity of a camera on a path, from three consecutive poses pos = (t, l, theta, phi) (the first frame passes pos_prev = pos, the
+ * last pos_next = pos: a one-sided difference) and the speed of light in path units per unit of t:
+ *   dt = t_next - t_prev, inv = 1.0 / (dt light_speed),
+ *   b_l = (l_next - l_prev) inv, b_theta = r(l) (theta_next - theta_prev) inv, b_phi = (r(l) sin theta) (phi_next - phi_prev) inv
+ * with the kind's r(l) and cv_math.h's sine at the middle pose, every product and difference rounded once, left to right; dt == 0 gives
+ * zero.  The angle differences are taken as they are: a path whose phi jumps by 2 pi between frames must be unwrapped by the caller.
+ * Nothing is checked against the speed of light here. */
+int curvis_camera_path_velocity(const curvis_metric *metric, const double pos_prev[4], const double pos[4], const double pos_next[4],
+                                double light_speed, double beta_out[3]);
 /* DiagonalSphericalMetric::relativistic_vector_to_direction (src/metrics.rs:339-349 with to_contravariant :190-203):
  * covariant momentum at `position` -> tangent-space direction (not normalised; z uses frame_field_22, as the
  * reference does). */

@@ -17,6 +17,8 @@ for _n in list(A.SYMBOLS):
 import curvis_amd
 from curvis_amd import skies
 ctx = curvis_amd.Context(0)
+for kv in filter(None, os.environ.get("AB_OPTIONS", "").split(",")):   # library options of every leg, e.g. AB_OPTIONS=projection=1
+    ctx.set_option(kv.split("=")[0], int(kv.split("=")[1]))
 ctx.set_sky(0, curvis_amd.SphericalImage(skies.smooth(512, 256, 0))); ctx.set_sky(1, curvis_amd.SphericalImage(skies.smooth(512, 256, 1)))
 cam = curvis_amd.Camera((0.0, 5.0, np.pi / 2, 0.0), (-1.0, 0.0, 0.0), (0.0, 0.0, 1.0), 15.0, 43.0, 1920, 1080)
 out = []
@@ -37,6 +39,11 @@ for _ in range(8):
     _, st = ctx.render_efficient(curvis_amd.EllisMetric(1.0), cams, 4096, 100.0, 0.05, 100, 100, 1e-5, 1e-5, download=False)
     ts.append(st.shade_ms / 32)
 out.append(float(np.median(ts[2:])))   # efficient renderer, 32 frames per call: the per-pixel kernel, per frame
+ts = []
+for _ in range(8):
+    _, st = ctx.render_direct(curvis_amd.EllisMetric(1.0), cam, 4096, 100.0, 0.05, download=False)
+    ts.append(st.kernel_ms)
+out.append(float(np.median(ts[2:])))   # direct renderer, one image
 print(" ".join("%%.4f" %% v for v in out))
 ''' % root
 res = {"old": [], "new": []}
@@ -49,5 +56,6 @@ for rnd in range(int(os.environ.get("ROUNDS", "4"))):
         print(name, r.stdout.strip() if vals else r.stderr[-400:], flush=True)
         if not vals: sys.exit("child failed (%d): nothing more is started on the GPU" % r.returncode)
         res[name].append(vals)
+print("spread of identical legs (max / min over the rounds - 1, per column):", {n: np.round(np.max(np.array(res[n]), axis=0) / np.min(np.array(res[n]), axis=0) - 1.0, 4).tolist() for n in res})
 for name in res:
-    print(name, "median over rounds [ellis x1, ellis x6 per frame, interstellar x1, efficient-image sampling kernels, efficient pixel kernel per frame of a 32-frame call] ms:", np.median(np.array(res[name]), axis=0))
+    print(name, "median over rounds [ellis x1, ellis x6 per frame, interstellar x1, efficient-image sampling kernels, efficient pixel kernel per frame of a 32-frame call, direct x1] ms:", np.median(np.array(res[name]), axis=0))
