@@ -9,8 +9,10 @@
  *                        context or a call holds is freed by destructors, on every return path
  *   render_host.h        struct curvis_ctx, with_kind / with_flag (metric kind and step flavour -> template arguments) and
  *                        with_launch_shape (those two, supersample, sky_filter and projection -> one tag type), prepare_call_shape
- *                        (what the three options make of a call, for all three renderers), kernel selection, render_impl = path decision +
- *                        render_chunk + relay_seat_belt, per-frame statistics
+ *                        (what the three options make of a call, for all three renderers), launch_integrate (the one launch of the
+ *                        kernel family the plan names), render_impl = facts of the call + render_chunk + relay_seat_belt, per-frame statistics
+ *   brute_plan.h         host only, plain C++ (g++ compiles it alone): from the facts of a brute call to its plan -- the refusals as a
+ *                        table, fused / relay, the kernel family -- and the launch shapes each family is instantiated for
  *   efficient_host.h     the adaptive sampler's driver (src/sampling.rs) over batched escape-angle launches, the device sampler's
  *                        slots and prefetch, per-pixel launch and statistics shared by the two
  *   kernels_png.h, png_host.h   PNG front end on the device: the frames in HBM -> one zlib stream per frame (src/rendering.rs:110, :311)
@@ -98,6 +100,7 @@
 #include "kernels_geodesic.h"
 #include "kernels_efficient.h"
 #include "hip_owned.h"
+#include "brute_plan.h"
 #include "render_host.h"
 #include "efficient_host.h"
 #include "png_codes.h"

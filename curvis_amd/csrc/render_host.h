@@ -1,6 +1,6 @@
-/* render_host.h -- host side of the per-pixel path: struct curvis_ctx, the metric / step-flavour dispatcher, launch selection
- * (static / relay / persistent), render_impl and its pieces (path decision, one chunk of frames, the relay seat belt), per-frame
- * statistics.
+/* render_host.h -- host side of the per-pixel path: struct curvis_ctx, the metric / step-flavour dispatcher, the one launch of the
+ * kernel family that brute_plan.h names, render_impl and its pieces (the facts of a call, one chunk of frames, the relay seat belt),
+ * per-frame statistics.
  * Part of the ONE translation unit curvis_hip.hip (included there, nowhere else). */
 #pragma once
 
@@ -317,8 +317,10 @@ size_t staged_cameras_bytes(uint32_t n, const cvk::CameraBoost *boost) { return 
 void stage_cameras(unsigned char *dst, const curvis_camera *cams, uint32_t n, const cvk::CameraBoost *boost);
 
 /* cams: the caller's n_frames cameras on entry, those the kernels run over on return (s.fine with ss > 1).  With the filter on, both
- * skies must be small enough for it; a fisheye whose image corner lies beyond the angle pi from the axis is refused; too_large is the renderer's message for a fine resolution that no longer fits 32 bits. */
-int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_frames, double delta, const char *too_large, CallShape &s) {
+ * skies must be small enough for it; a fisheye whose image corner lies beyond the angle pi from the axis is refused; too_large is the renderer's message for a fine resolution that no longer fits 32 bits.
+ * boost_prepared: s.boost is the call's already (render_impl, whose plan reads it before it comes here). */
+int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_frames, double delta, const char *too_large, CallShape &s,
+                       bool boost_prepared = false) {
   if (int rc = step_scale_kappa(ctx, delta, s.kappa, s.adapt)) return rc;
   s.ss = (uint32_t)ctx->supersample;
   s.filter = (uint32_t)ctx->sky_filter;
@@ -331,7 +333,8 @@ int prepare_call_shape(curvis_ctx *ctx, const curvis_camera *&cams, uint32_t n_f
       if (sky.texels && (sky.w > kSkyFilterMaxSide || sky.h > kSkyFilterMaxSide))
         return fail(ctx, CURVIS_E_INVALID, "sky_filter = 1: a sky of more than 2^23 texels per side (256 times its size must fit 32 bits)");
   s.projection = (uint32_t)ctx->projection;
-  if (int rc = prepare_camera_boost(ctx, cams, n_frames, s)) return rc;
+  if (!boost_prepared)
+    if (int rc = prepare_camera_boost(ctx, cams, n_frames, s)) return rc;
   if (s.projection == (uint32_t)cvk::PROJ_FISHEYE)
     for (uint32_t f = 0; f < n_frames; ++f) {
       const curvis_camera &c = cams[f];
@@ -579,8 +582,7 @@ SkyMipArgs sky_mip_args(const curvis_ctx *ctx) {
 }
 
 /* workgroup size of the static and relay kernels ("block_threads"; total_rays is a multiple of 64) */
-unsigned integrate_block_threads(const curvis_ctx *ctx, int kind) {
-  (void)kind;
+unsigned integrate_block_threads(const curvis_ctx *ctx) {
   const int bt = ctx->block_threads;
   return (bt == 64 || bt == 128 || bt == 256) ? (unsigned)bt : 256u;
 }
@@ -595,7 +597,7 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
   RelayArgs A;
   A.q = (RelayQueue *)ctx->d_rq.p;
   A.n_tiles = P.total_rays / 64ull;
-  const unsigned bt = integrate_block_threads(ctx, KIND);
+  const unsigned bt = integrate_block_threads(ctx);
   const unsigned long long fresh_blocks = relay_only ? 0ull : (P.total_rays + bt - 1ull) / bt;
   A.fresh_blocks = (unsigned)fresh_blocks;
   /* segment = 0.6 R / delta steps: an ordinary ray (about R / delta steps from a camera near the throat, +-10 %)
@@ -633,100 +635,6 @@ int launch_relay(curvis_ctx *ctx, const IntegrateParams &P, bool relay_only) {
   hipLaunchKernelGGL(kernel, dim3((unsigned)(fresh_blocks + relay_blocks)), dim3(bt), 0, ctx->stream, P, A);
   HIP_TRY(ctx, hipGetLastError());
   return CURVIS_OK;
-}
-
-/* One launch of the integrator.  relay: 0 no, 1 the relay kernel, 2 its relay-only re-launch.  The unfused static kernel and the
- * persistent one exist for SS = 1, FILTER = 0, PROJ = 0 only (their static_asserts): render_impl refuses the call shapes that would need
- * more. */
-template <int KIND, bool PHI, bool FAST, int SS, int FILTER, int PROJ, int ADAPT = 0>
-int launch_integrate(curvis_ctx *ctx, const IntegrateParamsAdapt &PA, bool fused, int relay) {
-  static_assert(!(PHI && FILTER == 2), "the debug dump's staged kernel has no mip-mapped lookup: render_impl refuses the call");
-  const IntegrateParams &P = PA; /* what every kernel but the ADAPT ones takes */
-  if constexpr (ADAPT == 0 && FILTER != 2 && KIND != cvk::METRIC_SCHWARZSCHILD) /* scaled steps, Heun steps, the mip-mapped lookup and the Schwarzschild kind never take the relay kernel (choose_render_path) */
-    if (relay && fused) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, P, relay == 2);
-  const unsigned bt = integrate_block_threads(ctx, KIND);
-  const dim3 grid((unsigned)((P.total_rays + bt - 1ull) / bt));
-  bool staged = false; /* launched a kernel that leaves the shading to shade_kernel */
-  if constexpr (ADAPT != 0) { /* the fused kernel, or the debug dump's staged one; render_impl refuses every other shape */
-    if constexpr (PHI) {
-      hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, false, 1, 0, 0, ADAPT>), grid, dim3(bt), 0, ctx->stream, PA);
-      staged = true;
-    }
-  } else if constexpr (SS == 1 && FILTER == 0 && PROJ == 0) {
-    bool persistent = false;
-    if constexpr (KIND != cvk::METRIC_SCHWARZSCHILD) /* no persistent kernel of the Schwarzschild kind: render_rays refuses variant = 0 */
-      if (ctx->variant == 0) {
-        int per_cu = ctx->blocks_per_cu;
-        if (per_cu <= 0) {
-          HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, geodesic_persistent<KIND, PHI, FAST>, 256, 0));
-          if (per_cu <= 0) per_cu = 1;
-        }
-        unsigned long long blocks = (unsigned long long)per_cu * (unsigned long long)ctx->prop.multiProcessorCount;
-        const unsigned long long max_useful = (P.total_rays + 255ull) / 256ull;
-        if (blocks > max_useful) blocks = max_useful;
-        if (blocks == 0) blocks = 1;
-        hipLaunchKernelGGL((geodesic_persistent<KIND, PHI, FAST>), dim3((unsigned)blocks), dim3(256), 0, ctx->stream, P);
-        persistent = staged = true;
-      }
-    if (!persistent && !fused) {
-      hipLaunchKernelGGL((geodesic_static<KIND, PHI, FAST, false>), grid, dim3(bt), 0, ctx->stream, P);
-      staged = true;
-    }
-  }
-  if constexpr (FILTER == 2) { /* option "sky_mipmap": the fused kernel alone, its argument with the level tables appended */
-    if constexpr (!PHI) {
-      WithSkyMip<IntegrateArgs<ADAPT>> PM;
-      static_cast<IntegrateArgs<ADAPT> &>(PM) = PA;
-      PM.mip = sky_mip_args(ctx);
-      hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, 2, PROJ, ADAPT>), grid, dim3(bt), 0, ctx->stream, PM);
-    }
-  } else {
-    if constexpr (ADAPT != 0 && !PHI) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ, ADAPT>), grid, dim3(bt), 0, ctx->stream, PA);
-    if constexpr (ADAPT == 0)
-      if (!staged) hipLaunchKernelGGL((geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ>), grid, dim3(bt), 0, ctx->stream, P);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  return CURVIS_OK;
-}
-
-/* A disc is set: the DISC form of the fused static kernel, its argument the plain form's with the disc appended.  Every call shape
- * that reaches here has one (render_impl refuses the debug dump, variant = 0 and fuse_shade = 0 while a disc is set). */
-template <int KIND, bool FAST, int SS, int FILTER, int PROJ, int ADAPT, int DISC = 1>
-int launch_disc(curvis_ctx *ctx, const IntegrateParamsAdapt &PA) {
-  const unsigned bt = integrate_block_threads(ctx, KIND);
-  const dim3 grid((unsigned)((PA.total_rays + bt - 1ull) / bt));
-  IntegrateArgsD<ADAPT, FILTER, DISC> PD;
-  if constexpr (DISC == 2) { /* the disc has a motion: sigma, G and the camera factors of the launch's frames (render_rays filled them) */
-    PD.motion.sigma = (double)ctx->disc_motion;
-    PD.motion.gain = ctx->disc_gain;
-    const cvk::CameraParams *cams0 = ctx->d_cams;
-    PD.motion.cam_factor = ctx->d_disc_cam + (PA.cams - cams0); /* the chunk's first frame, as PA.cams is */
-  }
-  static_cast<IntegrateArgs<ADAPT> &>(PD) = PA;
-  if constexpr (FILTER == 2) PD.mip = sky_mip_args(ctx);
-  PD.disc.texels = ctx->d_disc;
-  PD.disc.w = ctx->disc_w;
-  PD.disc.h = ctx->disc_h;
-  PD.disc.l_in = ctx->disc_l_in;
-  PD.disc.l_out = ctx->disc_l_out;
-  hipLaunchKernelGGL((geodesic_static<KIND, true, FAST, true, SS, FILTER, PROJ, ADAPT, DISC>), grid, dim3(bt), 0, ctx->stream, PD);
-  HIP_TRY(ctx, hipGetLastError());
-  return CURVIS_OK;
-}
-
-/* phi is integrated for the debug dump only, which is never fused, never relayed, never supersampled, never filtered and always in perspective
- * -- and by the DISC kernels, which are fused and take every option */
-int launch_integrate_any(curvis_ctx *ctx, int kind, bool phi, bool fast, bool fused, int relay, const IntegrateParamsAdapt &P, uint32_t ss,
-                         uint32_t filter, int adapt) {
-  return with_launch_shape(kind, fast, ss, filter, (uint32_t)P.projection, adapt, [&](auto S) {
-    using T = decltype(S);
-    if constexpr (T::KIND == cvk::METRIC_SCHWARZSCHILD) /* a motion: the DISC = 2 form, which exists for this kind alone (render_impl refuses the others) */
-      if (ctx->disc_set && ctx->disc_motion != 0) return launch_disc<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT, 2>(ctx, P);
-    if (ctx->disc_set) return launch_disc<T::KIND, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>(ctx, P);
-    if constexpr (T::SS == 1 && T::FILTER == 0 && T::PROJ == 0)
-      if (phi) return launch_integrate<T::KIND, true, T::FAST, 1, 0, 0, T::ADAPT>(ctx, P, false, 0);
-    return launch_integrate<T::KIND, false, T::FAST, T::SS, T::FILTER, T::PROJ, T::ADAPT>(ctx, P, fused, relay);
-  });
 }
 
 int launch_shade(curvis_ctx *ctx, int kind, bool debug, const ShadeParams &P) {
@@ -774,13 +682,40 @@ struct BruteCall {
   const cvk::CameraBoost *boost = nullptr; /* ... and then the frames' boosts, n_frames of them */
   double kappa = 0.0;            /* option "step_scale" for this call: RN(delta / L0) ... */
   int adapt = 0;                 /* ... and the kernels' ADAPT (CallShape) */
+  brute::Facts facts;            /* what the plan reads (brute_plan.h), but for relay_size_ok: choose_render_path's */
   uint32_t W = 0, H = 0;         /* H: the rows this call renders */
   size_t npix = 0, fb_bytes = 0;
 };
+static_assert(brute::KIND_SCHWARZSCHILD == CURVIS_METRIC_SCHWARZSCHILD && brute::KIND_SCHWARZSCHILD == cvk::METRIC_SCHWARZSCHILD, "brute_plan.h spells the kind out");
+/* the facts of a call as the context's options, its disc and the call's arguments give them; `moving` is known after prepare_camera_boost.
+ * Without a metric the disc's motion refuses nothing: the call is on its way to the null-argument refusal. */
+brute::Facts brute_facts(const curvis_ctx *ctx, const curvis_metric *metric, bool dump) {
+  brute::Facts f;
+  f.dump = dump;
+  f.variant = ctx->variant;
+  f.fuse_shade = ctx->fuse_shade != 0;
+  f.fast_math = ctx->fast_math != 0;
+  f.supersample = ctx->supersample > 1;
+  f.sky_filter = ctx->sky_filter != 0;
+  f.sky_mipmap = ctx->sky_mipmap != 0;
+  f.projection = ctx->projection != 0;
+  f.step_scale = ctx->step_scale != 0;
+  f.integrator = ctx->integrator != 0;
+  f.disc = !ctx->disc_set ? brute::DISC_NONE : ctx->disc_motion != 0 && metric ? brute::DISC_MOVING : brute::DISC_STATIC;
+  f.kind = metric ? metric->kind : CURVIS_METRIC_FLAT;
+  return f;
+}
+/* the plan's refusal, at the point of the call where it is due (brute::At) */
+int plan_refusal(curvis_ctx *ctx, const brute::Facts &facts, brute::At now) {
+  const brute::Plan plan = brute::plan(facts);
+  return plan.refusal && plan.at <= now ? fail(ctx, CURVIS_E_INVALID, plan.refusal) : CURVIS_OK;
+}
 int render_rays(curvis_ctx *ctx, BruteCall c);
-/* the same frames once more (the relay kernel's fall-backs and its checker): with the caller's outputs, or into d_fb only */
-int render_again(curvis_ctx *ctx, BruteCall c, bool deliver) {
+/* the same frames once more (the relay kernel's fall-backs and its checker): with the caller's outputs, or into d_fb only; the
+ * checker asks for the static kernel */
+int render_again(curvis_ctx *ctx, BruteCall c, bool deliver, bool static_only = false) {
   if (!deliver) c.rgb_out = nullptr, c.dbg_out = nullptr, c.stats = nullptr;
+  if (static_only) c.facts.variant = brute::STATIC_ONLY;
   return render_rays(ctx, c);
 }
 /* a piece's answer when the relay kernel has just been switched off for this context (waves that gave up, a checked launch that
@@ -789,16 +724,16 @@ constexpr int kRenderAgain = 1;
 
 /* which kernels render the call, and how many frames at a time */
 struct RenderPath {
-  bool fused, relay;
-  uint32_t chunk;     /* frames per launch */
-  size_t store_bytes; /* of the ray store: the relay kernel's staging area, or the unfused path's final states; 0 = none */
+  bool fused, relay;    /* the plan's (brute_plan.h) */
+  brute::Family family; /* of the kernel that integrates */
+  uint32_t chunk;       /* frames per launch */
+  size_t store_bytes;   /* of the ray store: the relay kernel's staging area, or the unfused path's final states; 0 = none */
 };
 RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
-  RenderPath p;
-  /* fused shading: static kernel, no debug dump (option "fuse_shade", default on) -- no ray store at all.
-   * Otherwise frames are rendered in chunks whose ray store stays below max_store_bytes. */
-  p.fused = ctx->variant != 0 && ctx->fuse_shade != 0 && c.dbg_out == nullptr;
-  /* relay kernel ("variant" = 2, and the automatic choice for big enough single images): end-game hand-over of
+  /* Fused shading (static kernel, no debug dump; option "fuse_shade", default on) has no ray store at all.  Otherwise frames are
+   * rendered in chunks whose ray store stays below max_store_bytes.  Which calls are fused, and which options keep a call from the
+   * relay kernel whatever its size: brute_plan.h (plan, kNoRelay).  Here are its size conditions.
+   * Relay kernel ("variant" = 2, and the automatic choice for big enough single images): end-game hand-over of
    * tiles; only launches of a few frames have a tail worth its staging area (56 B per ray) -- larger batches
    * use the static kernel, and so do frames too small to have a dispatch phase (measured against the static
    * kernel: 640x360 +2 %, 720x405 -9 %, 800x450 -9 %, 960x540 -15 %, 1280x720 -6 %, 1920x1080 -3..-5 %,
@@ -808,14 +743,13 @@ RenderPath choose_render_path(const curvis_ctx *ctx, const BruteCall &c) {
   const unsigned long long relay_min = ctx->relay_min_blocks >= 0 ? (unsigned long long)ctx->relay_min_blocks
                                                                    : 4ull * (unsigned long long)ctx->prop.multiProcessorCount;
   const size_t relay_staging = (size_t)tiles * 64u * kStoreBytesPerPixel;
-  /* option "step_scale": the static kernel -- the relay segments are sized in fixed-delta steps and its hand-over pattern was tuned on
-   * fixed-delta step counts (and the Schwarzschild kind, for which the relay kernel is not instantiated: its captured rays run ten times the steps of
-   * the others, a pattern the hand-over was never tuned on).  Option "integrator" = 1 likewise: there is no relay form of the Heun step.  Option "sky_mipmap" = 1: no relay
-   * form either (the epilogue is not where a single frame's time goes) */
-  /* a disc: the static kernel too -- there is no relay form of the DISC kernels */
-  /* a moving camera: the static kernel as well (render_impl) */
-  p.relay = !c.boost && !ctx->disc_set && c.metric->kind != CURVIS_METRIC_SCHWARZSCHILD && !c.adapt && c.filter != 2u && (ctx->variant == 2 || ctx->variant < 0) && !ctx->relay_disabled && p.fused && c.n_frames <= (uint32_t)ctx->relay_max_frames &&
-            relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
+  brute::Facts facts = c.facts;
+  facts.relay_size_ok = !ctx->relay_disabled && c.n_frames <= (uint32_t)ctx->relay_max_frames && relay_fresh_blocks >= relay_min && relay_staging <= ctx->max_store_bytes;
+  const brute::Plan plan = brute::plan(facts);
+  RenderPath p;
+  p.fused = plan.fused;
+  p.relay = plan.relay;
+  p.family = plan.family;
   p.chunk = c.n_frames;
   p.store_bytes = p.relay ? relay_staging : 0;
   if (!p.fused) {
@@ -831,12 +765,98 @@ struct RenderTotals { /* over the chunks of a call */
   double integrate_ms = 0.0, shade_ms = 0.0;
 };
 
+template <typename Arg>
+int launch_kernel(curvis_ctx *ctx, void (*kernel)(Arg), dim3 grid, dim3 block, const Arg &arg) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, arg);
+  HIP_TRY(ctx, hipGetLastError());
+  return CURVIS_OK;
+}
+/* the argument of a static kernel: the plain form's (PA, cut down to IntegrateParams where ADAPT = 0) with what FILTER = 2 and the
+ * DISC forms append */
+template <int ADAPT, int FILTER, int DISC = 0>
+IntegrateArgsD<ADAPT, FILTER, DISC> integrate_args(const curvis_ctx *ctx, const IntegrateParamsAdapt &PA) {
+  IntegrateArgsD<ADAPT, FILTER, DISC> A;
+  static_cast<IntegrateArgs<ADAPT> &>(A) = PA;
+  if constexpr (FILTER == 2) A.mip = sky_mip_args(ctx); /* option "sky_mipmap": the level tables */
+  if constexpr (DISC != 0) {
+    A.disc.texels = ctx->d_disc;
+    A.disc.w = ctx->disc_w;
+    A.disc.h = ctx->disc_h;
+    A.disc.l_in = ctx->disc_l_in;
+    A.disc.l_out = ctx->disc_l_out;
+  }
+  if constexpr (DISC == 2) { /* the disc has a motion: sigma, G and the camera factors of the launch's frames (render_rays filled them) */
+    A.motion.sigma = (double)ctx->disc_motion;
+    A.motion.gain = ctx->disc_gain;
+    const cvk::CameraParams *cams0 = ctx->d_cams;
+    A.motion.cam_factor = ctx->d_disc_cam + (PA.cams - cams0); /* the chunk's first frame, as PA.cams is */
+  }
+  return A;
+}
+
+/* One launch of the integrator: the kernel of the plan's family, in the call's launch shape.  Each family is instantiated for the
+ * shapes brute::family_exists names and for no other (the kernels' own static_asserts admit no more); the plan names no family that is
+ * absent for the call's shape (tests/test_brute_plan_host.py walks every call), so the refusal at the end is not reached.  phi is
+ * integrated for the debug dump and by the DISC kernels.  relay_only: the relay kernel's re-launch. */
+int launch_integrate(curvis_ctx *ctx, const BruteCall &c, brute::Family family, const IntegrateParamsAdapt &PA, bool relay_only = false) {
+  const unsigned bt = integrate_block_threads(ctx);
+  const dim3 grid((unsigned)((PA.total_rays + bt - 1ull) / bt)), block(bt);
+  return with_launch_shape(c.metric->kind, ctx->fast_math != 0, c.ss, c.filter, c.projection, c.adapt, [&](auto S) -> int {
+    using T = decltype(S);
+    using brute::Family;
+    constexpr int KIND = T::KIND, SS = T::SS, FILTER = T::FILTER, PROJ = T::PROJ, ADAPT = T::ADAPT;
+    constexpr bool FAST = T::FAST;
+    switch (family) {
+      case Family::Persistent:
+        if constexpr (brute::family_exists<T>(Family::Persistent))
+          return with_flag(c.dbg_out != nullptr, [&](auto PHI) -> int {
+            void (*const kernel)(const IntegrateParams) = geodesic_persistent<KIND, decltype(PHI)::value, FAST>;
+            int per_cu = ctx->blocks_per_cu;
+            if (per_cu <= 0) {
+              HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
+              if (per_cu <= 0) per_cu = 1;
+            }
+            unsigned long long blocks = (unsigned long long)per_cu * (unsigned long long)ctx->prop.multiProcessorCount;
+            const unsigned long long max_useful = (PA.total_rays + 255ull) / 256ull;
+            if (blocks > max_useful) blocks = max_useful;
+            if (blocks == 0) blocks = 1;
+            return launch_kernel(ctx, kernel, dim3((unsigned)blocks), dim3(256), integrate_args<0, 0>(ctx, PA));
+          });
+        break;
+      case Family::Unfused:
+        if constexpr (brute::family_exists<T>(Family::Unfused))
+          return with_flag(c.dbg_out != nullptr, [&](auto PHI) -> int {
+            return launch_kernel(ctx, geodesic_static<KIND, decltype(PHI)::value, FAST, false>, grid, block, integrate_args<0, 0>(ctx, PA));
+          });
+        break;
+      case Family::StagedAdapt:
+        if constexpr (brute::family_exists<T>(Family::StagedAdapt))
+          return launch_kernel(ctx, geodesic_static<KIND, true, FAST, false, 1, 0, 0, ADAPT>, grid, block, integrate_args<ADAPT, 0>(ctx, PA));
+        break;
+      case Family::Fused:
+        if constexpr (brute::family_exists<T>(Family::Fused))
+          return launch_kernel(ctx, geodesic_static<KIND, false, FAST, true, SS, FILTER, PROJ, ADAPT>, grid, block, integrate_args<ADAPT, FILTER>(ctx, PA));
+        break;
+      case Family::Relay: /* a grid of its own */
+        if constexpr (brute::family_exists<T>(Family::Relay)) return launch_relay<KIND, FAST, SS, FILTER, PROJ>(ctx, PA, relay_only);
+        break;
+      case Family::Disc:
+        if constexpr (brute::family_exists<T>(Family::Disc))
+          return launch_kernel(ctx, geodesic_static<KIND, true, FAST, true, SS, FILTER, PROJ, ADAPT, 1>, grid, block, integrate_args<ADAPT, FILTER, 1>(ctx, PA));
+        break;
+      case Family::DiscMotion:
+        if constexpr (brute::family_exists<T>(Family::DiscMotion))
+          return launch_kernel(ctx, geodesic_static<KIND, true, FAST, true, SS, FILTER, PROJ, ADAPT, 2>, grid, block, integrate_args<ADAPT, FILTER, 2>(ctx, PA));
+        break;
+    }
+    return fail(ctx, CURVIS_E_INVALID, "no kernel of the plan's family exists for this call's launch shape");
+  });
+}
+
 /* frames [f0, f0 + nf) of the call: parameters, the launch(es), the relay kernel's re-launch loop, counters -> statistics */
 int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, const cvk::MetricParams &MP, uint32_t f0, uint32_t nf,
                  RenderTotals &tot) {
   const bool relay = path.relay, fused = path.fused;
-  const bool phi = c.dbg_out != nullptr; /* phi is only read by the debug dump on this path */
-  const bool fast = ctx->fast_math != 0;
   FrameCounters FC;
   int rc = prepare_counters(ctx, nf, FC);
   if (rc) return rc;
@@ -872,7 +892,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   const char *trace_file = getenv("CURVIS_TRACE_FILE");
   size_t trace_words = (size_t)(P.total_rays / 64ull) * 4u;
   if (relay) trace_words = (size_t)(P.total_rays / 64ull) * 3u * 4u + 65536u * 16u; /* every wave of the grid */
-  if (trace_file && *trace_file && (ctx->variant != 0 || relay)) {
+  if (trace_file && *trace_file && path.family != brute::Family::Persistent) {
     if ((rc = trace.reserve(ctx, trace_words))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(trace, 0, trace_words * sizeof(unsigned long long), ctx->stream));
   }
@@ -889,7 +909,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
   Q.counters = FC;
 
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, relay ? 1 : 0, P, c.ss, c.filter, c.adapt);
+  rc = launch_integrate(ctx, c, path.family, P);
   if (rc) return rc;
   HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
   if (trace) {
@@ -935,7 +955,7 @@ int render_chunk(curvis_ctx *ctx, const BruteCall &c, const RenderPath &path, co
     if (hq->finished >= n_tiles) break;
     if (ctx->last_relay_launches++ > 64)
       return fail(ctx, CURVIS_E_HIP, "relay kernel: tiles still unfinished after 64 relay launches");
-    rc = launch_integrate_any(ctx, c.metric->kind, phi, fast, fused, 2, P, c.ss, c.filter, c.adapt);
+    rc = launch_integrate(ctx, c, path.family, P, true);
     if (rc) return rc;
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
@@ -1018,10 +1038,7 @@ int relay_seat_belt(curvis_ctx *ctx, const BruteCall &c) {
     if ((rc = ctx->d_fb.reserve(ctx, padded))) return rc;
   }
   const LastRenderStats relay_run(ctx);
-  const int saved = ctx->variant;
-  ctx->variant = 1; /* the static kernel */
-  rc = render_again(ctx, c, false);
-  ctx->variant = saved;
+  rc = render_again(ctx, c, false, true); /* the static kernel */
   if (rc) return rc;
   /* d_fb holds the static kernel's frame now */
   if (padded != fb_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->d_fb + fb_bytes, 0, padded - fb_bytes, ctx->stream));
@@ -1082,8 +1099,7 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
   int rc = curvis_metric_validate(c.metric);
   if (rc != CURVIS_OK) return fail(ctx, rc, "invalid metric parameters (src/metrics.rs:409-456)");
   if ((rc = schwarzschild_camera_check(ctx, c.metric, c.cams, c.n_frames))) return rc;
-  if (c.metric->kind == CURVIS_METRIC_SCHWARZSCHILD && ctx->variant == 0)
-    return fail(ctx, CURVIS_E_INVALID, "Schwarzschild metric: variant = 0 (the persistent kernel) is not built for this kind (set variant = -1, 1 or 2: the static kernel renders it)");
+  if ((rc = plan_refusal(ctx, c.facts, brute::AT_KIND))) return rc;
   const uint32_t H_full = c.cams[0].res_y;
   c.W = c.cams[0].res_x;
   if (c.W == 0 || H_full == 0) return fail(ctx, CURVIS_E_INVALID, "resolution must be greater than 0 (src/cameras.rs:98)");
@@ -1173,68 +1189,23 @@ int render_rays(curvis_ctx *ctx, BruteCall c) {
 
 /* the brute renderer's entry points, in the caller's units.  Option "supersample" = N > 1: the same call over the N times finer ray
  * grid -- cameras of N res_x x N res_y, the band in fine rows -- whose fused epilogues write res_x x res_y frames; every counter is
- * that of the fine render.  Call shapes without a tile-local resolve are refused. */
+ * that of the fine render.  Which combinations of options and call shape are refused, and in which words: brute_plan.h.  Its refusals
+ * fall due at three points (brute::At), between the argument checks and the refusals shared with the other renderers
+ * (prepare_call_shape), so that a doubly-wrong call reports the error it always did; render_rays has the third.  With every option
+ * off prepare_call_shape refuses nothing and leaves the call as it is. */
 int render_impl(curvis_ctx *ctx, const curvis_metric *metric, const curvis_camera *cams, uint32_t n_frames, uint32_t max_iterations,
                 double max_radius, double delta, uint8_t *rgb_out, curvis_ray_debug *dbg_out, curvis_stats *stats, uint32_t row_begin = 0,
                 uint32_t row_count = 0) {
   BruteCall c{metric, cams, n_frames, max_iterations, max_radius, delta, rgb_out, dbg_out, stats, row_begin, row_count, 1u, 0u, 0u};
-  /* a disc (include/curvis_hip.h) lives in the fused static kernel alone: the staged paths have no slot for a disc colour */
-  if (ctx && ctx->disc_set) {
-    if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "a disc is set: the debug dump shades from the ray store, which has no slot for a disc colour (remove the disc: curvis_ctx_set_disc with rgba = NULL)");
-    if (ctx->variant == 0) return fail(ctx, CURVIS_E_INVALID, "a disc is set: variant = 0 (the persistent kernel) shades from the ray store, which has no slot for a disc colour");
-    if (ctx->fuse_shade == 0) return fail(ctx, CURVIS_E_INVALID, "a disc is set: fuse_shade = 0 shades from the ray store, which has no slot for a disc colour");
-    if (ctx->disc_motion != 0 && metric && metric->kind != CURVIS_METRIC_SCHWARZSCHILD)
-      return fail(ctx, CURVIS_E_INVALID, "the disc motion is Keplerian and needs the Schwarzschild metric: in the other kinds g00 = -1, free matter is at rest and nothing orbits (set the motion to 0: curvis_ctx_set_disc_motion)");
-  }
-  if (!ctx || !metric || !cams || n_frames == 0 || (ctx->supersample <= 1 && !ctx->sky_filter && !ctx->sky_mipmap && !ctx->projection && !ctx->step_scale && !ctx->integrator && ctx->cam_beta.empty())) return render_rays(ctx, c);
-  /* a moving camera (curvis_ctx_set_camera_velocities) lives in the prologue of the fused static kernel, like the projections: the same
-   * three shapes are refused, under its name and before the others, while a frame of the call moves; and the disc's emission shift takes
-   * the camera to be at rest (include/curvis_hip.h), so a disc with a motion refuses the call too */
+  if (!ctx) return render_rays(ctx, c);
+  c.facts = brute_facts(ctx, metric, dbg_out != nullptr);
+  if (int rc = plan_refusal(ctx, c.facts, brute::AT_ENTRY)) return rc;
+  if (!metric || !cams || n_frames == 0) return render_rays(ctx, c);
   CallShape shape;
   if (int rc = prepare_camera_boost(ctx, cams, n_frames, shape)) return rc;
-  if (!shape.boost.empty()) {
-    if (dbg_out) return fail(ctx, CURVIS_E_INVALID, "camera velocity: the debug dump replays the static camera (clear the velocities: curvis_ctx_set_camera_velocities with n = 0)");
-    if (ctx->variant == 0) return fail(ctx, CURVIS_E_INVALID, "camera velocity: variant = 0 (the persistent kernel) has the static camera only");
-    if (ctx->fuse_shade == 0) return fail(ctx, CURVIS_E_INVALID, "camera velocity: fuse_shade = 0 (the unfused static kernel) has the static camera only");
-    if (ctx->disc_set && ctx->disc_motion != 0)
-      return fail(ctx, CURVIS_E_INVALID, "camera velocity: the emission shift of a moving disc takes the camera to be at rest (set the disc's motion to 0, or clear the velocities)");
-  }
-  /* only the fused kernels hold the projections, the filtered lookup and the tile-local resolve: three call shapes are refused, under
-   * the name of the projection when it is on, else of the filter when that is on, else of the supersampling when that is on.  The scaled
-   * steps (option "step_scale") exist in the fused kernels and in the debug dump's: a shape with a message of its own in the last
-   * column is refused under the option's name when none of the other three refuses it.  The option's fourth refusal, fast_math = 0,
-   * holds for all three renderers and is therefore made where they all pass, in step_scale_kappa (prepare_call_shape).  The Heun step
-   * (option "integrator" = 1) exists in the same kernels as the scaled steps and is refused for the same shapes, under its own name
-   * when "step_scale" is off.  The mip-mapped lookup (option "sky_mipmap" = 1) is refused for the filter's three shapes under its own
-   * name, before the others. */
-  const bool m = ctx->sky_mipmap != 0, f = ctx->sky_filter != 0, p = ctx->projection != 0, n = ctx->supersample > 1, a = ctx->step_scale != 0, h = ctx->integrator != 0;
-  const struct {
-    bool refused;
-    const char *mipmap, *projection, *filter, *supersample, *step_scale, *integrator;
-  } shapes[3] = {
-      {dbg_out != nullptr, "sky_mipmap = 1: the debug dump records the nearest lookup (set sky_mipmap = 0)", "projection != 0: the debug dump replays the perspective camera (set projection = 0)",
-       "sky_filter = 1: the debug dump records the nearest lookup (set sky_filter = 0)",
-       "supersample > 1: the debug dump has one record per ray, not per pixel (set supersample = 1)", nullptr, nullptr},
-      {ctx->variant == 0, "sky_mipmap = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
-       "projection != 0: variant = 0 (the persistent kernel) has the perspective camera only",
-       "sky_filter = 1: variant = 0 (the persistent kernel) shades from the ray store, which has the nearest lookup only",
-       "supersample > 1: variant = 0 (the persistent kernel) stages single rays and has no tile-local resolve",
-       "step_scale != 0: variant = 0 (the persistent kernel) takes the reference's fixed step only",
-       "integrator = 1: variant = 0 (the persistent kernel) takes the reference's Euler step only"},
-      {ctx->fuse_shade == 0, "sky_mipmap = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
-       "projection != 0: fuse_shade = 0 (the unfused static kernel) has the perspective camera only",
-       "sky_filter = 1: fuse_shade = 0 shades from the ray store, which has the nearest lookup only",
-       "supersample > 1: fuse_shade = 0 shades single rays from the ray store and has no tile-local resolve",
-       dbg_out ? nullptr : "step_scale != 0: fuse_shade = 0 (the unfused static kernel) takes the reference's fixed step only outside the debug dump",
-       dbg_out ? nullptr : "integrator = 1: fuse_shade = 0 (the unfused static kernel) takes the reference's Euler step only outside the debug dump"}};
-  for (const auto &s : shapes)
-    if (s.refused) {
-      const char *why = m ? s.mipmap : p ? s.projection : f ? s.filter : n ? s.supersample : nullptr;
-      if (!why && a) why = s.step_scale;
-      if (!why && h) why = s.integrator;
-      if (why) return fail(ctx, CURVIS_E_INVALID, why);
-    }
-  if (int rc = prepare_call_shape(ctx, c.cams, n_frames, delta, "frame or batch too large", shape)) return rc;
+  c.facts.moving = !shape.boost.empty();
+  if (int rc = plan_refusal(ctx, c.facts, brute::AT_SHAPE)) return rc;
+  if (int rc = prepare_call_shape(ctx, c.cams, n_frames, delta, "frame or batch too large", shape, true)) return rc;
   c.boost = shape.boost.empty() ? nullptr : shape.boost.data();
   c.kappa = shape.kappa;
   c.adapt = shape.adapt;

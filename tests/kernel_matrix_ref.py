@@ -1,7 +1,7 @@
 """The brute renderer's kernel lattice: every form of the fused static kernel -- metric kind x step form x supersample x lookup x
 projection, 384 cells, each once plain and once as a DISC form -- and the 96 forms of the relay kernel, with the reference frame and
-counters of every cell.  The enumeration is written from the static asserts of geodesic_static and from launch_disc / launch_integrate
-(curvis_amd/csrc/render_host.h); nothing of it is read from the product.
+counters of every cell.  The enumeration is written from the static asserts of geodesic_static and from the launch shapes each kernel
+family exists for (curvis_amd/csrc/brute_plan.h family_exists, render_host.h launch_integrate); nothing of it is read from the product.
 
 The reference is tests/disc_ref.py's over tests/ref_compose.py, which is compositional: a ray is walked by the oracle's own step (the
 library's host accessors for the Schwarzschild kind) under the step option, and the lookup and the supersampling are pure functions of a

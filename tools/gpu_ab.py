@@ -44,6 +44,15 @@ for _ in range(8):
     _, st = ctx.render_direct(curvis_amd.EllisMetric(1.0), cam, 4096, 100.0, 0.05, download=False)
     ts.append(st.kernel_ms)
 out.append(float(np.median(ts[2:])))   # direct renderer, one image
+import time
+small = curvis_amd.Camera((0.0, 5.0, np.pi / 2, 0.0), (-1.0, 0.0, 0.0), (0.0, 0.0, 1.0), 15.0, 43.0, 160, 90)
+for c, n in ((cam, 24), (small, 400)):   # the whole call by the host's clock: 1080p, and a frame small enough for the host's share to show
+    ts = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        ctx.render_brute(curvis_amd.EllisMetric(1.0), c, 4096, 100.0, 0.05, download=False)
+        ts.append((time.perf_counter() - t0) * 1e3)
+    out.append(float(np.median(ts[n // 4:])))
 print(" ".join("%%.4f" %% v for v in out))
 ''' % root
 res = {"old": [], "new": []}
@@ -58,4 +67,4 @@ for rnd in range(int(os.environ.get("ROUNDS", "4"))):
         res[name].append(vals)
 print("spread of identical legs (max / min over the rounds - 1, per column):", {n: np.round(np.max(np.array(res[n]), axis=0) / np.min(np.array(res[n]), axis=0) - 1.0, 4).tolist() for n in res})
 for name in res:
-    print(name, "median over rounds [ellis x1, ellis x6 per frame, interstellar x1, efficient-image sampling kernels, efficient pixel kernel per frame of a 32-frame call, direct x1] ms:", np.median(np.array(res[name]), axis=0))
+    print(name, "median over rounds [ellis x1, ellis x6 per frame, interstellar x1, efficient-image sampling kernels, efficient pixel kernel per frame of a 32-frame call, direct x1, whole brute call by the host's clock at 1080p, the same at 160x90] ms:", np.median(np.array(res[name]), axis=0))
